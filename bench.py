@@ -16,27 +16,45 @@ per-GPU coverage maps (the only collective; every GPU is otherwise an
 independent shard with seed + rank). One process per GPU; `value` = testcases
 all ranks executed / max-over-ranks wall time of the K timed steps.
 
+A plain run (`--gpus 1 --steps K --warmup W`) does only that: build the tlv
+snapshot, open the node, warm up, time the K steps, print the result line.
+Everything below marked (--full) takes runs of its own and happens only with
+`--full`; `--no-cpu` / `--no-legs` then leave parts of it out.
+
+`--dump-outputs DIR` writes what a caller of the timed path holds after its
+last step, as float64 .npy files (all values are integers below 2^53, so exact):
+  stats.npy      the node's counters after the last timed step, DUMP_COUNTERS
+                 order (wtfnode_stats)
+  last_step.npy  the same counters' change over the last timed step alone
+  corpus.npy     one row (size, 48-bit digest of name and content) per file
+                 the node has written to the target's outputs/, sorted by name
+  crashes.npy    the same for crashes/ (one file per unique crash)
+The snapshot, seed corpus and seed 1337 are fixed, so the same arguments give
+the same inputs on every run and two builds can be compared file for file.
+Rank r > 0 of a multi-GPU run writes <name>_r<r>.npy.
+
 Also on the line (N=1, rank 0):
-  roofline      k_run (the dominant kernel) on the headline workload:
+  roofline      k_run (the dominant kernel) on the headline workload, from
+                the timed steps' own counters:
                 algorithmic bytes per launch (instruction bytes + data bytes
                 read + written, counted per lane by the kernel) /
                 average launch duration (HIP events on the engine's stream);
                 `traffic` and VALU utilisation from the committed rocprofv3 PMC
                 summary of the same workload (profiles/pmc_tlv_k_run.json).
-  cpu_baseline  the oracle twin (`oracle/wtf_twin`: the C restatement behind
+  cpu_baseline  (--full) the oracle twin (`oracle/wtf_twin`: the C restatement behind
                 Backend_t, "port" — bochscpu is unbuildable) as one
                 `wtf_twin fuzz` process per host core, same module, mutator
                 and seed scheme, over a bounded wall window.
-  hevd          BASELINE.json configs[4] on one GPU: the synthetic ring-0 HEVD
+  hevd          (--full) BASELINE.json configs[4] on one GPU: the synthetic ring-0 HEVD
                 snapshot with the I/O manager's IRP path and benign-majority
                 seeds (wtf_amd/tools/hevd_io.py), the hevd module, libFuzzer's
                 mutator (bit-exact restatement), --limit 10000000, --max_len
                 1028, >= 10 s of node wall time, with its own roofline, crash
                 share and twin baseline.
-  hevd_bare     the same on the bare look-alike (wtf_amd/tools/hevd.py: the
+  hevd_bare     (--full) the same on the bare look-alike (wtf_amd/tools/hevd.py: the
                 handlers called from the system-call entry, ~300 instructions
                 per exec, mostly crashing traffic), the round-5 HEVD leg.
-  syn           BASELINE.json configs[1]: the ring-3 ALU/branch/load-store
+  syn           (--full) BASELINE.json configs[1]: the ring-3 ALU/branch/load-store
                 interpreter microbench, 65,536 lanes, with its roofline and the
                 C oracle's rate on the host cores.
 """
@@ -94,9 +112,16 @@ def parse():
     ap.add_argument("--leg-seconds", type=float, default=10.0, help="GPU wall window of the hevd leg")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall window of each CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the host CPU share (see cpu_cores)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="headline only (skip hevd / syn)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="besides the headline, the CPU baselines and the hevd / "
+                    "hevd_bare / syn legs (N=1); without it only the headline runs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: leave the hevd / hevd_bare / syn legs out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the node's outputs after the last timed step to DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 GPUS_PER_NODE = 8  # an MI355X node (BASELINE.json: 1/2/4/8 GPUs)
@@ -390,6 +415,49 @@ def syn_leg(lanes: int, limit: int, steps: int, device: int) -> dict:
                                  acc["steps"], acc["retired"])}
 
 
+# ----------------------------------------------------------------- --dump-outputs
+# the node's counters that the inputs alone decide (no times, and none of the
+# backend's launch / wave-step counts, which follow the measured schedule)
+DUMP_COUNTERS = ("execs", "retired", "batches", "crashes", "timeouts", "cr3", "errors", "coverage", "corpus",
+                 "merged_rips", "error_retired", "breakpoint_hits")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_counters(stats: dict) -> np.ndarray:
+    return np.array([float(stats[k]) for k in DUMP_COUNTERS], dtype=np.float64)
+
+
+def dump_dir_rows(path: str, max_rows: int) -> np.ndarray:
+    """One (size, digest) row per file of `path`, sorted by name; the digest is
+    the first 48 bits of sha256(name NUL content), exact in a float64. Above
+    max_rows, a fixed seeded sample of the rows (in the same order)."""
+    import hashlib
+
+    names = sorted(os.listdir(path)) if os.path.isdir(path) else []
+    if len(names) > max_rows:
+        keep = np.sort(np.random.default_rng(1337).choice(len(names), max_rows, replace=False))
+        names = [names[i] for i in keep]
+    rows = np.zeros((len(names), 2), dtype=np.float64)
+    for i, n in enumerate(names):
+        with open(os.path.join(path, n), "rb") as f:
+            data = f.read()
+        rows[i] = (len(data), int.from_bytes(hashlib.sha256(n.encode() + b"\0" + data).digest()[:6], "big"))
+    return rows
+
+
+def dump_outputs(d: str, rank: int, target: str, before_last: dict, after_last: dict):
+    """The files of --dump-outputs (see the module docstring). Called after
+    node.close(), which flushes the crash writer."""
+    os.makedirs(d, exist_ok=True)
+    sfx = f"_r{rank}" if rank else ""
+    max_rows = DUMP_MAX_BYTES // (4 * 16)  # two directories, 16 bytes a row, half the budget
+    after, before = dump_counters(after_last), dump_counters(before_last)
+    for name, arr in (("stats", after), ("last_step", after - before),
+                      ("corpus", dump_dir_rows(os.path.join(target, "outputs"), max_rows)),
+                      ("crashes", dump_dir_rows(os.path.join(target, "crashes"), max_rows))):
+        np.save(os.path.join(d, f"{name}{sfx}.npy"), arr)
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -404,16 +472,16 @@ def main():
 
 
 def run(a, rank, world, local, tmp):
-    # snapshots + CPU baselines first (rank 0, N = 1), before anything touches the GPU
+    # snapshots + CPU baselines first (--full, rank 0, N = 1), before anything touches the GPU
     tlv_dir = build_target("tlv_server", os.path.join(tmp, "tlv"))
-    legs = rank == 0 and world == 1 and not a.no_legs
+    legs = a.full and rank == 0 and world == 1 and not a.no_legs
     hevd_dir = build_target("hevd", os.path.join(tmp, "hevd")) if legs else None
     bare_dir = build_target("hevd_bare", os.path.join(tmp, "hevd_bare")) if legs else None
     cores, core_info = cpu_cores()
     if a.cpu_threads:
         cores = a.cpu_threads
     cpu = {}
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         cpu["tlv_server"] = twin_baseline("tlv_server", tlv_dir, a.cpu_seconds, cores, a.limit)
         if legs:
             cpu["hevd"] = twin_baseline("hevd", hevd_dir, a.cpu_seconds, cores, a.hevd_limit)
@@ -445,8 +513,10 @@ def run(a, rank, world, local, tmp):
     s0 = node.stats()
     sum0 = node.summary()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for _ in range(a.steps - 1):
         node.step()
+    s_last = node.stats()  # a copy of the host-side counters, for --dump-outputs' last_step
+    node.step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -463,6 +533,8 @@ def run(a, rank, world, local, tmp):
     timed["backend"] = {k: round(v - sum0["backend"][k], 3) for k, v in summary["backend"].items()
                         if isinstance(v, (int, float)) and k in sum0["backend"]}
     node.close()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, tlv_dir, s_last, s1)
 
     if rank == 0:
         out = {

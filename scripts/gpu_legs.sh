@@ -1,9 +1,10 @@
 # Every bench leg (tlv headline, hevd, syn; no CPU baselines) at each regroup setting in $RG_LIST.
 set -o pipefail
-cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out
+OUT=${OUT:-bench_out}  # where the logs go
+cd "$(dirname "$0")/.." && mkdir -p $OUT
 for R in ${RG_LIST:-0 256}; do
-  WTFGPU_REGROUP_STEPS=$R timeout -k 10 400 python -u bench.py --no-cpu --regroup-steps $R --lanes ${LANES:-131072} > gpurun_out/legs_$R.log 2>&1 || { echo FAIL $R; tail -20 gpurun_out/legs_$R.log; exit 1; }
-  tail -1 gpurun_out/legs_$R.log | python -c "
+  WTFGPU_REGROUP_STEPS=$R timeout -k 10 400 python -u bench.py --full --no-cpu --regroup-steps $R --lanes ${LANES:-131072} > $OUT/legs_$R.log 2>&1 || { echo FAIL $R; tail -20 $OUT/legs_$R.log; exit 1; }
+  tail -1 $OUT/legs_$R.log | python -c "
 import json,sys; d=json.loads(sys.stdin.read())
 print('R=$R tlv', round(d['value']), 'lpws', round(d['lanes_per_wave_step'],1))
 for k in ('hevd','syn'):
