@@ -261,11 +261,7 @@ __device__ __forceinline__ void wr(Lane &L, u32 r, u32 sz, u64 v) {
 // A TLB miss or a first write to a shared page -> L.miss = 2 with the address:
 // k_run serves it in registers (fast_fill) and retries. Everything else ->
 // L.miss = 1, the slow step takes over.
-#ifndef WTFGPU_FAST_NB
-#define WTFGPU_FAST_NB 1  // branch-free translation and unconditional loads in the fast path
-#endif
-#if WTFGPU_FAST_NB
-// The same decisions as selects, without per-lane branches (each early return
+// The decisions are selects, without per-lane branches (each early return
 // was an exec-mask region): the first failure of the attempt sets L.miss.
 __device__ __forceinline__ u8 *fxlate(Lane &L, u64 va, u32 sz, int acc) {
   u64 td;
@@ -293,28 +289,6 @@ __device__ __forceinline__ u64 load_le2(const u8 *p, u32 sz) {
   const u64 v = off ? (lo >> (8 * off)) | (hi << (64 - 8 * off)) : lo;
   return v & szmask(sz);
 }
-#else
-__device__ __forceinline__ u8 *fxlate(Lane &L, u64 va, u32 sz, int acc) {
-  u64 td;
-  const bool w = acc == ACC_W;
-  if ((va & 0xfff) + sz > 4096) {
-    L.miss = 1;
-    return nullptr;
-  }
-  const bool hit = tlb_get(L, va >> 12, td);
-  if (!hit || (perm_ok(L, td, acc) && w && (td & (T_PRIV | T_PT)) == 0)) {
-    L.miss = 2;
-    L.miss_va = va;
-    L.miss_acc = (u32)acc;
-    return nullptr;
-  }
-  if (!perm_ok(L, td, acc) || (w && ((td & (T_PRIV | T_PT)) != T_PRIV))) {
-    L.miss = 1;
-    return nullptr;
-  }
-  return (u8 *)(uintptr_t)(td & ~0xfffull) + (va & 0xfff);
-}
-#endif
 
 // 16 / 32 bytes at p (inside one page): aligned words, funnel-shifted when p
 // is not 8-byte aligned (the word past the operand is read only then, and it
@@ -449,22 +423,11 @@ __device__ __forceinline__ int fast_exec(const FastMem &M, Lane &L, const FOp &f
     if (!kRegOnly && (F & (FF_MR_A | FF_MR_B))) {
       const u32 rsz = (F & (FF_PUSH | FF_POP)) ? 8 : (op == FO_MOVX ? fo_szb(f) : sz);
       mp = fxlate(L, addr, rsz, rmw ? ACC_W : ACC_R);
-#if WTFGPU_FAST_NB
       const u64 v = load_le2(mp ? mp : M.safe, rsz);  // a missed lane reads the zero page, unused
       L.pend += mp ? rsz : 0;
       if (F & FF_MR_A) a = mp ? v : a;
       else b = mp ? v : b;
       ok = mp != nullptr;
-#else
-      if (mp) {
-        const u64 v = load_le(mp, rsz);
-        L.pend += rsz;
-        if (F & FF_MR_A) a = v;
-        else b = v;
-      } else {
-        ok = false;
-      }
-#endif
     }
     // ---- compute (pure)
     switch (op) {
@@ -528,15 +491,6 @@ __device__ __forceinline__ int fast_exec(const FastMem &M, Lane &L, const FOp &f
     }
   }
   // ---- commit (rsp first: pop rsp ends with the popped value)
-#if WTFGPU_FAST_WB_ALWAYS
-  const u64 nrsp = !ok ? rsp : (F & FF_PUSH) ? rsp - 8 : (F & FF_POP) ? rsp + 8 + (op == FO_RET ? f.imm : 0) : rsp;
-  RS(L, 4, nrsp);
-  const u32 wi = fo_ra(f) & 15, hs = (fo_ra(f) & FR_HB) >> 2;
-  const u64 old = R(L, wi), mk = szmask(sz) << hs;
-  // wr(): 8 / 4 bytes replace (4 zero-extends), 2 / 1 merge into the old value
-  const u64 nv = (ok && (F & FF_WRA)) ? (sz >= 4 ? (res & mk) : ((old & ~mk) | ((res << hs) & mk))) : old;
-  RS(L, wi, nv);
-#else
   // (written under the op's uniform flags: ops that write no register skip
   // the indexed read-back and write)
   if (F & (FF_PUSH | FF_POP)) RS(L, 4, !ok ? rsp : (F & FF_PUSH) ? rsp - 8 : rsp + 8 + (op == FO_RET ? f.imm : 0));
@@ -546,7 +500,6 @@ __device__ __forceinline__ int fast_exec(const FastMem &M, Lane &L, const FOp &f
     // wr(): 8 / 4 bytes replace (4 zero-extends), 2 / 1 merge into the old value
     RS(L, wi, ok ? (sz >= 4 ? (res & mk) : ((old & ~mk) | ((res << hs) & mk))) : old);
   }
-#endif
   if (ok && (F & FF_FLAGS)) L.rflags = fl;
   return ok ? X_OK : X_FAULT;
 }

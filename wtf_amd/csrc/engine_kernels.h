@@ -1,0 +1,564 @@
+// engine_kernels.h — the plumbing kernels around k_run: lane restore,
+// host-driven lane memory, bulk lane services and coverage services.
+//
+// Device half of engine.hip (see engine_run.h); included nowhere else.
+#pragma once
+#include "engine_run.h"
+
+namespace {
+
+// ---------------------------------------------------------------- restore
+struct InitState {
+  u64 g[16];
+  u64 rip, rflags, fsb, gsb;
+  LaneSys sys;
+};
+
+// Registers, system state and overlay of one lane back to the snapshot (the
+// dirty-list reset: overlays dropped, nothing copied).
+__device__ __forceinline__ void restore_lane(const Dev &P, const InitState &s, const wtfgpu_regs_t *full0,
+                                             wtfgpu_regs_t *full, u32 lane) {
+  const u64 N = P.nlanes;
+  full[lane] = *full0;
+#pragma unroll
+  for (int i = 0; i < 16; i++) P.gpr[i * N + lane] = s.g[i];
+  P.rip[lane] = s.rip;
+  P.rflags[lane] = s.rflags;
+  P.fs_base[lane] = s.fsb;
+  P.gs_base[lane] = s.gsb;
+  P.icount[lane] = 0;
+  P.nbytes[lane] = 0;
+  P.status[lane] = WTFGPU_RUNNING;
+  P.lflags[lane] = 0;
+  P.sys[lane] = s.sys;
+  P.ov_count[lane] = 0;
+  tlb_stale(P, lane);
+  if (P.rd_seed) P.rd_seed[lane] = P.rd_seed0;  // bochscpu_backend.cc:1030
+  if (P.trace_cnt) P.trace_cnt[lane] = 0;
+  if (P.edge_cnt) P.edge_cnt[2 * (u64)lane] = P.edge_cnt[2 * (u64)lane + 1] = 0;
+  if (g_tn.buf) {
+    g_tn.pos[lane] = g_tn.ipos[lane] = g_tn.cpos[lane] = 0;
+    g_tn.last[lane] = ~0ull;
+    g_tn.mute[lane] = 0;
+  }
+  if (P.cov_rip) {
+    P.lane_gen[lane] += 1;
+    P.cov_cnt[lane] = 0;
+    P.cov_overflow[lane] = 0;
+  }
+}
+
+// Streaming form: a lane list.
+__global__ void k_restore_list(Dev P, const InitState *S, const wtfgpu_regs_t *full0, wtfgpu_regs_t *full,
+                               const u32 *lanes, u32 n) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const InitState s = *S;
+  restore_lane(P, s, full0, full, lanes[t]);
+}
+
+__global__ void k_restore(Dev P, const InitState *S, const wtfgpu_regs_t *full0, wtfgpu_regs_t *full, u32 first,
+                          u32 count) {
+  const u32 tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 lane = first + tid;
+  if (tid >= count || lane >= P.nlanes) return;
+  const u64 N = P.nlanes;
+  const InitState s = *S;
+  full[lane] = *full0;  // cold architectural state (read/write_regs only)
+#pragma unroll
+  for (int i = 0; i < 16; i++) P.gpr[i * N + lane] = s.g[i];
+  P.rip[lane] = s.rip;
+  P.rflags[lane] = s.rflags;
+  P.fs_base[lane] = s.fsb;
+  P.gs_base[lane] = s.gsb;
+  P.icount[lane] = 0;
+  P.nbytes[lane] = 0;
+  P.status[lane] = WTFGPU_RUNNING;
+  P.lflags[lane] = 0;
+  P.sys[lane] = s.sys;
+  P.ov_count[lane] = 0;  // the dirty-list reset: overlays dropped, nothing copied
+  tlb_stale(P, lane);
+  if (P.rd_seed) P.rd_seed[lane] = P.rd_seed0;  // bochscpu_backend.cc:1030
+  if (P.trace_cnt) P.trace_cnt[lane] = 0;
+  if (P.edge_cnt) P.edge_cnt[2 * (u64)lane] = P.edge_cnt[2 * (u64)lane + 1] = 0;
+  if (g_tn.buf) {
+    g_tn.pos[lane] = g_tn.ipos[lane] = g_tn.cpos[lane] = 0;
+    g_tn.last[lane] = ~0ull;
+    g_tn.mute[lane] = 0;
+  }
+  if (P.cov_rip) {       // the lane's coverage set empties
+    P.lane_gen[lane] += 1;
+    P.cov_cnt[lane] = 0;
+    P.cov_overflow[lane] = 0;
+  }
+}
+
+// ---------------------------------------------------------------- host-driven lane memory
+// One thread per lane with pending writes (records sorted by lane). op: 0 write virt.
+struct WriteRec {
+  u32 lane, len;
+  u64 gva, data_off;
+};
+
+__device__ __forceinline__ void lane_min_load(const Dev &P, u32 lane, Lane &L) {
+  const LaneSys s = P.sys[lane];
+  L.cr0 = s.cr0;
+  L.cr3 = s.cr3;
+  L.efer = s.efer;
+  L.cpl = 0;  // host accesses are not subject to user checks (VirtTranslate has none)
+  L.simd = 0;
+  L.ovn = P.ov_count[lane];
+  L.bloom = 0;
+  for (u32 k = 0; k < L.ovn; k++) L.bloom |= bloom_bit(P.ov_gpfn[(u64)k * P.nlanes + lane]);
+  L.lane = lane;
+  L.status = WTFGPU_RUNNING;
+  L.nbytes = 0;
+  tlb_flush(L);
+  L.tnext = 0;
+  L.miss = L.miss_acc = L.flush = L.pend = 0;
+  L.nodeliver = 0;
+}
+
+// Host-side translation (bochscpu_mem_virt_translate semantics: present bits
+// only, no permission checks).
+__device__ __forceinline__ bool host_walk(const Dev &P, Lane &L, u64 va, u64 &gpa) {
+  u64 table = L.cr3 & 0x000ffffffffff000ull;
+  bool priv;
+  u64 e = 0, pmask = 0xfff;
+  for (int level = 3; level >= 0; level--) {
+    const u8 *pg = phys_page(P, L.lane, L.ovn, L.bloom, table >> 12, priv);
+    e = *(const u64 *)(pg + ((va >> (12 + 9 * level)) & 0x1ff) * 8);
+    if (!(e & 1)) return false;
+    if ((level == 1 || level == 2) && (e & 0x80)) {
+      pmask = level == 2 ? 0x3fffffffull : 0x1fffffull;
+      break;
+    }
+    table = e & 0x000ffffffffff000ull;
+  }
+  gpa = ((e & 0x000ffffffffff000ull) & ~pmask) | (va & pmask);
+  return true;
+}
+
+// The same write by one 64-thread block (the control is uniform, every
+// thread computes it; the page copy and the bytes are spread over the block).
+__device__ __forceinline__ bool lane_phys_write_block(const Dev &P, Lane &L, u64 gpa, const u8 *src, u64 len, u32 lid) {
+  while (len) {
+    const u64 off = gpa & 0xfff;
+    u64 n = 4096 - off;
+    if (n > len) n = len;
+    bool priv;
+    const u8 *pg = phys_page(P, L.lane, L.ovn, L.bloom, gpa >> 12, priv);
+    u8 *dst = (u8 *)pg;
+    if (!priv) {
+      if (L.ovn >= P.K) return false;
+      dst = P.ov_data + ((u64)L.lane * P.K + L.ovn) * WTFGPU_PAGE_SIZE;
+      const uint4 *s4 = (const uint4 *)pg;
+      uint4 *d4 = (uint4 *)dst;
+      for (u32 i = lid; i < 256; i += 64) d4[i] = s4[i];
+      if (lid == 0) P.ov_gpfn[(u64)L.ovn * P.nlanes + L.lane] = (u32)(gpa >> 12);
+      __syncthreads();  // the copy before the patch (and the slot before later lookups)
+      L.ovn++;
+      L.bloom |= bloom_bit(gpa >> 12);
+    }
+    for (u64 i = lid; i < n; i += 64) dst[off + i] = src[i];
+    __syncthreads();
+    src += n;
+    gpa += n;
+    len -= n;
+  }
+  return true;
+}
+
+// Host-handler writes, one 64-thread block per lane, records in order.
+__global__ void k_apply_writes(Dev P, const WriteRec *recs, const u32 *starts, u32 nlanes_w, const u8 *data,
+                               i32 *status_out, u32 phys) {
+  const u32 t = blockIdx.x, lid = threadIdx.x;
+  if (t >= nlanes_w) return;
+  const u32 r0 = starts[t], r1 = starts[t + 1];
+  const u32 lane = recs[r0].lane;
+  Lane L;
+  lane_min_load(P, lane, L);
+  for (u32 r = r0; r < r1; r++) {
+    const WriteRec w = recs[r];
+    u64 va = w.gva, left = w.len;
+    const u8 *src = data + w.data_off;
+    i32 st = 0;
+    while (left) {
+      const u64 off = va & 0xfff;
+      u64 n = 4096 - off;
+      if (n > left) n = left;
+      u64 gpa = va;
+      if (!phys && !host_walk(P, L, va, gpa)) {
+        st = WTFGPU_ERR_TRANSLATE;
+        break;
+      }
+      if (!lane_phys_write_block(P, L, gpa, src, n, lid)) {
+        st = WTFGPU_ERR_OOM;
+        break;
+      }
+      va += n;
+      src += n;
+      left -= n;
+    }
+    if (lid == 0) status_out[r] = st;
+  }
+  if (lid == 0) {
+    P.ov_count[lane] = L.ovn;
+    tlb_stale(P, lane);
+  }
+}
+
+// Host-injected exception per lane (PageFaultsMemoryIfNeeded): delivered
+// through the guest IDT now; the lane resumes at the handler.
+__global__ void k_inject_fault(Dev P, const u32 *lanes, const u64 *addrs, u32 n, u32 vector, u32 error, i32 *ok) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const u32 lane = lanes[t];
+  u32 glo[16], ghi[16];
+  Lane L;
+  L.glo = glo;
+  L.ghi = ghi;
+  load_lane(P, lane, L);
+  L.status = WTFGPU_EXIT_FAULT;
+  L.exvec = vector;
+  L.exerr = error;
+  L.exaddr = addrs[t];
+  const bool d = deliver_fault(P, L);
+  ok[t] = d ? 1 : 0;
+  if (d && g_tn.buf) {  // Tenet: the injected exception
+    g_tn.ipos[lane] = g_tn.pos[lane];
+    tn_regs(P, L);
+  }
+  if (d) {
+    store_lane(P, L);
+    tlb_stale(P, lane);
+    P.lflags[lane] = 0;
+  }
+}
+
+// The declared insert of a lane list (wtfgpu_set_insert), after the feed
+// scatter: lanes without a feed are left alone. The writes are not CPU
+// accesses (Tenet does not log them).
+__global__ void k_insert(Dev P, wtfgpu_insert_t ins, const u32 *lanes, u32 first, u32 n) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const u32 lane = lanes ? lanes[t] : first + t;
+  if (P.feed_pos[lane] == ~0ull || P.status[lane] != WTFGPU_RUNNING) return;
+  u32 glo[16], ghi[16];
+  Lane L;
+  L.glo = glo;
+  L.ghi = ghi;
+  load_lane(P, lane, L);
+  if (g_tn.buf) tn_mute(lane);
+  insert_apply(P, L, ins);
+  if (g_tn.buf) tn_unmute(lane, 0, 0, 0, false);
+  store_lane(P, L);
+  store_tlb(P, L);
+}
+
+// Lane status (+ skip-breakpoint-once flag) for a lane list (resume / stop).
+__global__ void k_set_status(Dev P, const u32 *lanes, u32 n, u32 status, const u8 *skip) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const u32 lane = lanes[t];
+  P.status[lane] = status;
+  if (skip) P.lflags[lane] = skip[t] ? 1u : (g_tn.buf ? 2u : 0u);  // 2: Tenet entry at the next launch
+}
+
+// Single-lane memory services for the host proxy.
+// op 0: translate (out u64 gpa), 1: read phys, 2: write phys, 3: read virt, 4: write virt
+__global__ void k_lane_mem(Dev P, u32 lane, u32 op, u64 addr, u64 len, u8 *buf, i64 *result) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  Lane L;
+  lane_min_load(P, lane, L);
+  i64 rc = 0;
+  if (op == 0) {
+    u64 gpa;
+    rc = host_walk(P, L, addr, gpa) ? (i64)gpa : -1;
+  } else if (op == 1 || op == 3) {
+    u64 a = addr;
+    for (u64 i = 0; i < len;) {
+      u64 gpa = a;
+      if (op == 3 && !host_walk(P, L, a, gpa)) {
+        rc = -1;
+        break;
+      }
+      u64 n = 4096 - (a & 0xfff);
+      if (n > len - i) n = len - i;
+      bool priv;
+      const u8 *pg = phys_page(P, L.lane, L.ovn, L.bloom, gpa >> 12, priv);
+      for (u64 k = 0; k < n; k++) buf[i + k] = pg[(gpa & 0xfff) + k];
+      i += n;
+      a += n;
+    }
+  } else {
+    u64 a = addr;
+    for (u64 i = 0; i < len;) {
+      u64 gpa = a;
+      if (op == 4 && !host_walk(P, L, a, gpa)) {
+        rc = -1;
+        break;
+      }
+      u64 n = 4096 - (a & 0xfff);
+      if (n > len - i) n = len - i;
+      if (!lane_phys_write(P, L, gpa, buf + i, n)) {
+        rc = -2;
+        break;
+      }
+      i += n;
+      a += n;
+    }
+    P.ov_count[lane] = L.ovn;
+    tlb_stale(P, lane);
+  }
+  *result = rc;
+}
+
+// ---------------------------------------------------------------- bulk lane services
+// GPRs + rip + rflags (18 u64, that order) of a lane list, gathered / scattered.
+__global__ void k_gather_gprs(Dev P, const u32 *lanes, u32 n, u64 *out) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const u64 N = P.nlanes, l = lanes[t];
+  for (int i = 0; i < 16; i++) out[(u64)t * 18 + i] = P.gpr[i * N + l];
+  out[(u64)t * 18 + 16] = P.rip[l];
+  out[(u64)t * 18 + 17] = P.rflags[l];
+}
+__global__ void k_scatter_gprs(Dev P, const u32 *lanes, u32 n, const u64 *in) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const u64 N = P.nlanes, l = lanes[t];
+  for (int i = 0; i < 16; i++) P.gpr[i * N + l] = in[(u64)t * 18 + i];
+  P.rip[l] = in[(u64)t * 18 + 16];
+  P.rflags[l] = in[(u64)t * 18 + 17];
+}
+// Dirty lists of a lane list: out[t * (K + 1)] = count, then the gpfns.
+__global__ void k_gather_dirty(Dev P, const u32 *lanes, u32 n, u32 *out) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const u32 l = lanes[t], cnt = P.ov_count[l];
+  u32 *o = out + (u64)t * (P.K + 1);
+  o[0] = cnt;
+  for (u32 k = 0; k < cnt && k < P.K; k++) o[1 + k] = P.ov_gpfn[(u64)k * P.nlanes + l];
+}
+// Lane views of physical pages (overlay copy, else snapshot, else zeros): one
+// 256-thread block per (lane, gpa) request, 16 bytes per thread.
+// `len` bytes (<= 256, within one page) at (lane, gpa) from each lane's view:
+// one 64-thread block per record, 4 bytes per thread.
+__global__ void k_gather_bytes(Dev P, const u32 *lanes, const u64 *gpas, u32 n, u32 len, u8 *out) {
+  const u32 r = blockIdx.x;
+  if (r >= n) return;
+  const u32 l = lanes[r];
+  const u64 gpa = gpas[r];
+  const u32 ovn = P.ov_count[l];
+  u64 bloom = 0;
+  for (u32 k = 0; k < ovn; k++) bloom |= bloom_bit(P.ov_gpfn[(u64)k * P.nlanes + l]);
+  bool priv;
+  const u8 *src = phys_page(P, l, ovn, bloom, gpa >> 12, priv) + (gpa & 0xfff);
+  for (u32 i = threadIdx.x; i < len; i += blockDim.x) out[(u64)r * len + i] = src[i];
+}
+
+__global__ void k_gather_pages(Dev P, const u32 *lanes, const u64 *gpas, u32 n, u8 *out) {
+  const u32 r = blockIdx.x;
+  if (r >= n) return;
+  const u32 l = lanes[r];
+  const u64 gpfn = gpas[r] >> 12;
+  const u32 ovn = P.ov_count[l];
+  u64 bloom = 0;
+  for (u32 k = 0; k < ovn; k++) bloom |= bloom_bit(P.ov_gpfn[(u64)k * P.nlanes + l]);
+  bool priv;
+  const uint4 *src = (const uint4 *)phys_page(P, l, ovn, bloom, gpfn, priv);
+  ((uint4 *)(out + (u64)r * WTFGPU_PAGE_SIZE))[threadIdx.x] = src[threadIdx.x];
+}
+
+// ---------------------------------------------------------------- coverage services
+// The coverage sets of a lane list (lanes == nullptr: lanes first + i), one
+// block per lane, compacted into (lane, rip) pairs.
+__global__ void k_cov_collect(Dev P, const u32 *lanes, u32 first, u32 n, u32 *out_lane, u64 *out_rip, u64 cap,
+                              unsigned long long *n_out, u32 *ovf) {
+  const u32 i = blockIdx.x;
+  if (i >= n) return;
+  const u32 lane = lanes ? lanes[i] : first + i;
+  const u32 g = P.lane_gen[lane];
+  const u64 base = (u64)lane * P.H;
+  for (u32 k = threadIdx.x; k < P.H; k += blockDim.x) {
+    if (P.cov_gen[base + k] != g) continue;
+    const unsigned long long pos = atomicAdd(n_out, 1ull);
+    if (pos < cap) {
+      out_lane[pos] = lane;
+      out_rip[pos] = P.cov_rip[base + k];
+    }
+  }
+  if (threadIdx.x == 0 && P.cov_overflow[lane]) atomicOr(ovf, 1u);
+}
+
+// The coverage sets of the stopped lanes of [first, first + count) (status
+// neither RUNNING nor IDLE: the lanes a slice finished or left at a host
+// breakpoint), compacted as k_cov_collect does (wtfgpu_prefetch_coverage).
+// One wave per lane; an empty set (cov_cnt 0, the common case once the
+// coverage has settled) costs one load.
+__global__ void k_cov_collect_stopped(Dev P, u32 first, u32 count, u32 *out_lane, u64 *out_rip, u64 cap,
+                                      unsigned long long *n_out, u32 *ovf) {
+  const u32 i = blockIdx.x * 4 + (threadIdx.x >> 6), lid = threadIdx.x & 63;
+  if (i >= count) return;
+  const u32 lane = first + i;
+  const u32 st = P.status[lane];
+  if (st == WTFGPU_RUNNING || st == WTFGPU_EXIT_IDLE) return;
+  if (P.cov_overflow[lane] && lid == 0) atomicOr(ovf, 1u);
+  if (P.cov_cnt[lane] == 0) return;
+  const u32 g = P.lane_gen[lane];
+  const u64 base = (u64)lane * P.H;
+  for (u32 k = lid; k < P.H; k += 64) {
+    if (P.cov_gen[base + k] != g) continue;
+    const unsigned long long pos = atomicAdd(n_out, 1ull);
+    if (pos < cap) {
+      out_lane[pos] = lane;
+      out_rip[pos] = P.cov_rip[base + k];
+    }
+  }
+}
+
+// Rdrand seeds of a lane list: gathered into / scattered from buf.
+__global__ void k_lane_seeds(Dev P, const u32 *lanes, u32 n, u64 *buf, int write) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (write) P.rd_seed[lanes[i]] = buf[i];
+  else buf[i] = P.rd_seed[lanes[i]];
+}
+
+// STOP_ARGS arguments of a lane list (6 u64 each).
+__global__ void k_stop_args(Dev P, const u32 *lanes, u32 n, u64 *out) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * 6) return;
+  out[i] = P.stop_args[(u64)lanes[i / 6] * 6 + i % 6];
+}
+
+// Exit records of lanes [first, first + count) (wtfgpu_read_exits).
+__global__ void k_pack_exits(Dev P, u32 first, u32 count, wtfgpu_exit_t *out) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const u32 lane = first + i;
+  wtfgpu_exit_t e;
+  e.status = P.status[lane];
+  e.vector = e.error = e.opcode = 0;
+  e.addr = 0;
+  if (e.status == WTFGPU_EXIT_FAULT) {
+    const ExitInfo x = P.exinfo[lane];
+    e.vector = x.vector;
+    e.error = x.error;
+    e.addr = x.addr;
+    e.opcode = x.cpl;
+  } else if (e.status == WTFGPU_EXIT_UNIMPLEMENTED) {
+    e.opcode = P.exinfo[lane].opcode;
+  }
+  e.rip = P.rip[lane];
+  e.icount = P.icount[lane];
+  out[i] = e;
+}
+
+// Regrouping keys: running lanes by rip (lanes at one rip become neighbours,
+// so one wave step serves them all), every other lane after them (their
+// waves find nothing to run and leave at once).
+// They also count the running lanes (P.stat[3]): a launch with none returns at once.
+__global__ void k_regroup_keys(Dev P, u32 first, u32 count, u32 *keys, u32 *lanes) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = i < count;
+  const u32 lane = first + (in ? i : 0);
+  const bool run = in && P.status[lane] == WTFGPU_RUNNING;
+  const u64 m = __ballot(run);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long *)&P.stat[3], (unsigned long long)__popcll(m));
+  if (!in) return;
+  const u32 r = (u32)P.rip[lane] & 0xffffffu;  // 24 key bits: three radix passes
+  keys[i] = run ? (r == 0xffffffu ? r - 1 : r) : 0xffffffu;
+  lanes[i] = lane;
+}
+
+// Empty the coverage sets of a lane list (generation bump: O(1) per lane).
+__global__ void k_cov_clear(Dev P, const u32 *lanes, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u32 lane = lanes[i];
+  P.lane_gen[lane] += 1;
+  P.cov_cnt[lane] = 0;
+  P.cov_overflow[lane] = 0;
+}
+
+// Bytes set in the coverage map but not in its shadow (what a MAX all-reduce
+// brought in from other shards since the last look), as byte indices; with
+// `write`, the shadow catches up with the map. Sixteen bytes per thread.
+__global__ void k_cov_absorb(const u8 *map, u8 *shadow, u64 n16, u64 *out_idx, u64 cap,
+                             unsigned long long *count, int write) {
+  const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n16) return;
+  const uint4 m = ((const uint4 *)map)[t], s = ((const uint4 *)shadow)[t];
+  if (m.x == s.x && m.y == s.y && m.z == s.z && m.w == s.w) return;
+  const u32 mw[4] = {m.x, m.y, m.z, m.w}, sw[4] = {s.x, s.y, s.z, s.w};
+  for (int w = 0; w < 4; w++)
+    for (int b = 0; b < 4; b++)
+      if (((mw[w] >> (8 * b)) & 0xff) && !((sw[w] >> (8 * b)) & 0xff)) {
+        const unsigned long long pos = atomicAdd(count, 1ull);
+        if (write && pos < cap) out_idx[pos] = t * 16 + w * 4 + b;
+      }
+  if (write) ((uint4 *)shadow)[t] = m;
+}
+
+// A merged map from the other shards (bytes are 0 / 1, so OR is the MAX):
+// the deferred shard merge (CoverageExchange_t::MergeEnd); k_cov_absorb then
+// reports what it added.
+__global__ void k_cov_merge_in(uint4 *map, const uint4 *src, u64 n16) {
+  const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n16) return;
+  const uint4 a = map[t], b = src[t];
+  if ((b.x & ~a.x) | (b.y & ~a.y) | (b.z & ~a.z) | (b.w & ~a.w)) map[t] = uint4{a.x | b.x, a.y | b.y, a.z | b.z, a.w | b.w};
+}
+
+// Per-lane feed regions (streaming): `n` lanes, lane lanes[i] gets
+// len[i] bytes from src + off[i] at its region.
+// Lane i's feed: bytes [off[i], off[i + 1]) of src into the lane's region, its
+// read position and end set; a lane without a feed (has[i] = 0) or with one
+// larger than its region keeps none (the host handler serves it).
+__global__ void k_feed_scatter(u8 *feed, u64 stride, const u32 *lanes, const u64 *off, const u8 *has, u32 n,
+                               const u8 *src, u64 *feed_pos, u64 *feed_end) {
+  const u32 i = blockIdx.x;
+  if (i >= n) return;
+  const u32 lane = lanes[i];
+  const u64 o = off[i], len = off[i + 1] - o;
+  const bool keep = (!has || has[i]) && len <= stride;
+  if (threadIdx.x == 0) {
+    feed_pos[lane] = keep ? (u64)lane * stride : ~0ull;
+    feed_end[lane] = keep ? (u64)lane * stride + len : 0;
+  }
+  if (!keep) return;
+  u8 *dst = feed + (u64)lane * stride;
+  const u8 *sp = src + o;
+  for (u64 k = threadIdx.x; k < len; k += blockDim.x) dst[k] = sp[k];
+}
+
+__global__ void k_cov_commit(Dev P, const u64 *rips, u64 n) {
+  const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n || !P.code_keys) return;
+  const u64 rip = rips[t];
+  u32 h = (u32)mix64(rip >> 12) & P.code_mask;
+  for (u32 i = 0; i <= P.code_mask; i++) {
+    const u64 k = P.code_keys[h];
+    if (k == rip >> 12) {
+      const u64 at = (u64)P.code_slot[h] * WTFGPU_PAGE_SIZE + (rip & 0xfff);
+      P.cov_map[at] = 1;
+      P.cov_shadow[at] = 1;  // this shard's own find: not reported by absorb
+      return;
+    }
+    if (k == EMPTY_KEY) break;
+    h = (h + 1) & P.code_mask;
+  }
+  // not a code byte of a code page (a rip elsewhere, an edge): the extra set,
+  // kept at most 3/4 full (a value that does not fit is logged again later)
+  if (!P.extra_keys || rip == EMPTY_KEY) return;
+  u32 g = (u32)mix64(rip) & P.extra_mask;
+  for (u32 i = 0; i <= P.extra_mask / 4; i++) {
+    const unsigned long long prev = atomicCAS((unsigned long long *)&P.extra_keys[g], EMPTY_KEY, rip);
+    if (prev == EMPTY_KEY || prev == rip) return;
+    g = (g + 1) & P.extra_mask;
+  }
+}
+
+}  // namespace
