@@ -786,8 +786,17 @@ bool GpuBackend_t::classify(const std::vector<uint32_t> &pending, uint32_t first
     if (hit[pi] == 1) hits.push_back(pending[pi]);
     if (hit[pi] == 2) named.push_back(pending[pi]);
   }
-  if (named.empty()) return true;
-  // device StopWithArgs actions: the handler's Stop(Result(GetArg(0..5)))
+  name_stop_args(named, first, ex, done, out, stop_args);
+  return true;
+}
+
+// Device StopWithArgs actions: the handler's Stop(Result(GetArg(0..5))) for
+// each lane of `named` (stop_args: the range's prefetched arguments, 6 per
+// lane from `first`; else they are read here).
+void GpuBackend_t::name_stop_args(const std::vector<uint32_t> &named, uint32_t first, const wtfgpu_exit_t *ex,
+                                  std::vector<uint8_t> &done, std::vector<LaneResult> *out,
+                                  const uint64_t *stop_args) {
+  if (named.empty()) return;
   std::vector<uint64_t> args(named.size() * 6);
   bool ok = true;
   if (stop_args) {
@@ -812,7 +821,6 @@ bool GpuBackend_t::classify(const std::vector<uint32_t> &pending, uint32_t first
     done[l - first] = 1;
   }, named.size() >= 2048);
   stats_.err_other += bad;
-  return true;
 }
 
 // Final state of every finished lane (`ex` holds the last round's exits of
@@ -820,12 +828,31 @@ bool GpuBackend_t::classify(const std::vector<uint32_t> &pending, uint32_t first
 bool GpuBackend_t::fill_results(const std::vector<uint32_t> &lanes, uint32_t first,
                                 const wtfgpu_exit_t *ex, const std::vector<uint8_t> &done,
                                 std::vector<LaneResult> *out, std::vector<uint32_t> *finished) {
-  const auto tg = Clock::now();
   std::vector<uint32_t> fin;
   for (uint32_t l : lanes)
     if (done[l - first]) fin.push_back(l);
   if (finished) finished->insert(finished->end(), fin.begin(), fin.end());
-  if (!out) return true;
+  return !out || fill_lanes(fin, first, ex, *out);
+}
+
+void GpuBackend_t::fill_lane(uint32_t l, const wtfgpu_exit_t &e, LaneResult &r) {
+  const LaneView &v = views_[l];  // untouched since its reset: no result, no fault
+  const bool t = touched_[l] != 0;
+  r.result = t && v.result ? std::move(*v.result) : TestcaseResult_t(Ok_t());  // the view is reset at refill
+  if (t && v.handler_fault) {  // U43: an engine error, never a named crash
+    r.result = Crash_t();
+    r.error = true;
+    r.handler_fault = true;
+    stats_.err_handler++;
+  }
+  r.rip = e.rip;
+  r.icount = e.icount;
+  r.exit_status = e.status;
+}
+
+bool GpuBackend_t::fill_lanes(const std::vector<uint32_t> &fin, uint32_t first, const wtfgpu_exit_t *ex,
+                              std::vector<LaneResult> &out) {
+  const auto tg = Clock::now();
   std::vector<uint64_t> regs;
   // run stats of [lo, hi) (run mode): byte, dirty-page and edge counters
   uint32_t lo = 0, hi = 0;
@@ -846,16 +873,8 @@ bool GpuBackend_t::fill_results(const std::vector<uint32_t> &lanes, uint32_t fir
     }
   }
   HostPool::Get().For(fin.size(), 1024, [&](size_t i) {
-    LaneResult &r = (*out)[fin[i]];
-    const LaneView &v = views_[fin[i]];  // untouched since its reset: no result, no fault
-    const bool t = touched_[fin[i]] != 0;
-    r.result = t && v.result ? std::move(*v.result) : TestcaseResult_t(Ok_t());  // the view is reset at refill
-    if (t && v.handler_fault) {  // U43: an engine error, never a named crash
-      r.result = Crash_t();
-      r.error = true;
-      r.handler_fault = true;
-      stats_.err_handler++;
-    }
+    LaneResult &r = out[fin[i]];
+    fill_lane(fin[i], ex[fin[i] - first], r);
     if (want_gprs_) {
       memcpy(r.gprs, &regs[i * 18], 18 * 8);
       r.rip = r.gprs[16];
@@ -864,11 +883,7 @@ bool GpuBackend_t::fill_results(const std::vector<uint32_t> &lanes, uint32_t fir
       r.dirty = std::min(dc[k], overlay_pages_);
       r.edges = ec[2 * k];
       r.edges_new = ec[2 * k + 1];
-    } else {
-      r.rip = ex[fin[i] - first].rip;
     }
-    r.icount = ex[fin[i] - first].icount;
-    r.exit_status = ex[fin[i] - first].status;
   }, fin.size() >= 2048);
   stats_.regs_ms += ms_since(tg);
   return true;
@@ -1483,8 +1498,9 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
     tag_.assign(nlanes_, 0);
     tc_bytes_.assign(nlanes_, 0);
     lres_.assign(nlanes_, LaneResult{});
-    lres_stale_.assign(nlanes_, 0);
+    plain_.assign(nlanes_, 0);
     const uint32_t n = parts_n();
+    done_.assign((nlanes_ + n - 1) / n + 1, 0);
     parts_.assign(n, Part{});
     for (uint32_t p = 0; p < n; p++) {
       Part &Q = parts_[p];
@@ -1506,125 +1522,186 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
   if (pipelined && P.launched && !harvest_part(P, Target, Out, Slots)) return false;
   const auto ti = Clock::now();
   stats_.harvest_ms += std::chrono::duration<double, std::milli>(ti - t0).count();
-  // ---- refill
-  std::vector<uint32_t> fresh;
-  std::vector<std::pair<const uint8_t *, size_t>> tcs;
-  fresh.reserve(std::min<size_t>(In.size(), P.hi - P.lo));
-  tcs.reserve(fresh.capacity());
-  {  // the lowest free lanes, in order
+  // ---- refill: the lowest free lanes, in order
+  std::vector<uint32_t> &fresh = fresh_;
+  {
     const size_t take = std::min(In.size(), P.free.size());
     fresh.assign(P.free.begin(), P.free.begin() + (std::ptrdiff_t)take);
     P.free.erase(P.free.begin(), P.free.begin() + (std::ptrdiff_t)take);
-    tcs.resize(take);
-    for (size_t i = 0; i < take; i++) tcs[i] = {In[i].data, In[i].size};
   }
   if (Taken) *Taken = fresh.size();
   stats_.fresh_ms += ms_since(ti);
   if (!fresh.empty()) {
     if (wtfgpu_restore_lanes(ctx_, fresh.data(), (uint32_t)fresh.size())) return false;
     stats_.restore_dev_ms += ms_since(ti);
-    // a prepared insert (Target_t::PrepareInsert) the backend takes is applied
-    // here, with the lane's module state reset as before an InsertTestcase;
-    // the other lanes call InsertTestcase below
-    std::vector<uint8_t> prepared(fresh.size(), 0);
-    HostPool::Get().For(fresh.size(), 256, [&](size_t i) {
-      const uint32_t l = fresh[i];
-      // a view the host touched goes back to the initial state; an untouched
-      // one still is in it (the common case: no host handler ran on the lane)
-      if (touched_[l]) reset_view(l);
-      pf_[l] = PrepFeed{};
-      busy_[l] = 1;
-      tag_[l] = In[i].tag;
-      tc_bytes_[l] = In[i].size;
-      lres_stale_[l] = 1;  // its last result may not be consumed yet (this call's Out)
-      const StreamTestcase_t &T = In[i];
-      switch (T.prep) {
-        case PreparedInsert_t::Call: return;
-        case PreparedInsert_t::Failed: view(l).result = Crash_t("insert-testcase-failed"); break;
-        case PreparedInsert_t::Nothing: break;
-        case PreparedInsert_t::Feed:  // SetFeed would refuse it: InsertTestcase keeps its host path
-          if (!feed_action_ || T.prep_size > kFeedRegion) return;
-          pf_[l] = PrepFeed{T.prep_data, (uint32_t)T.prep_size, 1, 0};
-          break;
-        case PreparedInsert_t::Insert:  // as SetInsert
-          if (!insert_action_ || T.size + 4 > kFeedRegion) return;
-          pf_[l] = PrepFeed{T.data, (uint32_t)T.size, 1, 1};
-          break;
+    // One pass over the fresh lanes, a chunk of them per loop index: the
+    // lane's view and streaming state are reset; a prepared insert
+    // (Target_t::PrepareInsert) the backend takes is applied, with the lane's
+    // module state reset as before an InsertTestcase, and its feed's size
+    // noted (the chunk's sum with it); the other lanes are listed for the
+    // InsertTestcase calls below, the lanes that hold a result already for
+    // the device stop.
+    const size_t n = fresh.size();
+    const bool feeds = feed_action_ || insert_action_;
+    constexpr size_t kChunk = 1024;
+    const size_t chunks = (n + kChunk - 1) / kChunk;
+    if (rchunks_.size() < chunks) rchunks_.resize(chunks);
+    if (flen_.size() < n) {
+      flen_.resize(n);
+      fhas_.resize(n);
+      foff_.resize(n + 1);
+    }
+    HostPool::Get().For(chunks, 1, [&](size_t c) {
+      RefillChunk &C = rchunks_[c];
+      C.call.clear();
+      C.pre.clear();
+      C.bytes = 0;
+      const size_t hi = std::min(n, (c + 1) * kChunk);
+      for (size_t i = c * kChunk; i < hi; i++) {
+        const uint32_t l = fresh[i];
+        // a view the host touched goes back to the initial state; an untouched
+        // one still is in it (the common case: no host handler ran on the lane)
+        if (touched_[l]) reset_view(l);
+        PrepFeed f{};
+        busy_[l] = 1;
+        tag_[l] = In[i].tag;
+        tc_bytes_[l] = In[i].size;
+        const StreamTestcase_t &T = In[i];
+        bool prepared = true;
+        switch (T.prep) {
+          case PreparedInsert_t::Call: prepared = false; break;
+          case PreparedInsert_t::Failed:
+            view(l).result = Crash_t("insert-testcase-failed");
+            C.pre.push_back(l);
+            break;
+          case PreparedInsert_t::Nothing: break;
+          case PreparedInsert_t::Feed:  // SetFeed would refuse it: InsertTestcase keeps its host path
+            if (!feed_action_ || T.prep_size > kFeedRegion)
+              prepared = false;
+            else
+              f = PrepFeed{T.prep_data, (uint32_t)T.prep_size, 1, 0};
+            break;
+          case PreparedInsert_t::Insert:  // as SetInsert
+            if (!insert_action_ || T.size + 4 > kFeedRegion)
+              prepared = false;
+            else
+              f = PrepFeed{T.data, (uint32_t)T.size, 1, 1};
+            break;
+        }
+        pf_[l] = f;
+        flen_[i] = f.has ? f.len + (f.ins ? 4 : 0) : 0;
+        fhas_[i] = f.has;
+        C.bytes += flen_[i];
+        if (!prepared) {
+          C.call.push_back((uint32_t)i);
+          continue;
+        }
+        if (Slots) Slots->ResetLane(l);
       }
-      if (Slots) Slots->ResetLane(l);
-      prepared[i] = 1;
-    });
+    }, n >= 512);
     recycle_arenas();  // reset_view's drop_staged ran inside the loop
     const auto tm = Clock::now();
     stats_.restore_ms += std::chrono::duration<double, std::milli>(tm - ti).count();
-    std::vector<uint32_t> call;
-    std::vector<std::pair<const uint8_t *, size_t>> call_tcs;
-    for (size_t i = 0; i < fresh.size(); i++)
-      if (!prepared[i]) {
-        call.push_back(fresh[i]);
-        call_tcs.push_back(tcs[i]);
+    call_.clear();
+    pre_.clear();
+    for (size_t c = 0; c < chunks; c++) {
+      call_.insert(call_.end(), rchunks_[c].call.begin(), rchunks_[c].call.end());
+      pre_.insert(pre_.end(), rchunks_[c].pre.begin(), rchunks_[c].pre.end());
+    }
+    stats_.prepared += n - call_.size();
+    std::vector<uint32_t> call(call_.size());
+    if (!call_.empty()) {  // InsertTestcase on the host for the lanes no prepared insert covers
+      std::vector<std::pair<const uint8_t *, size_t>> call_tcs(call_.size());
+      for (size_t k = 0; k < call_.size(); k++) {
+        call[k] = fresh[call_[k]];
+        call_tcs[k] = {In[call_[k]].data, In[call_[k]].size};
       }
-    stats_.prepared += fresh.size() - call.size();
-    if (!call.empty()) {
       std::vector<uint8_t> ok;
       insert_lanes(Target, call, call_tcs, Slots, ok);
-      for (size_t i = 0; i < call.size(); i++)
-        if (!ok[i]) view(call[i]).result = Crash_t("insert-testcase-failed");
+      for (size_t k = 0; k < call.size(); k++)
+        if (!ok[k]) view(call[k]).result = Crash_t("insert-testcase-failed");
     }
     const auto tu = Clock::now();
     stats_.module_ms += std::chrono::duration<double, std::milli>(tu - tm).count();
     if (flush_lanes(call)) return false;
-    if (feed_action_ || insert_action_) {
+    if (!call_.empty()) {
+      // their feeds (a view's SetFeed / SetInsert bytes) and results, now known
+      std::vector<uint32_t> pre_call;
+      for (size_t k = 0; k < call_.size(); k++) {
+        const uint32_t i = call_[k], l = call[k];
+        if (!touched_[l]) continue;
+        const LaneView &v = views_[l];
+        flen_[i] = (uint32_t)v.feed.size();
+        fhas_[i] = v.has_feed;
+        rchunks_[i / kChunk].bytes += flen_[i];
+        if (v.result.has_value()) pre_call.push_back(l);
+      }
+      if (!pre_call.empty()) {  // both ascending
+        tmp_lanes_.resize(pre_.size() + pre_call.size());
+        std::merge(pre_.begin(), pre_.end(), pre_call.begin(), pre_call.end(), tmp_lanes_.begin());
+        pre_.swap(tmp_lanes_);
+      }
+    }
+    if (feeds) {
       const auto tf = Clock::now();
-      const size_t n = fresh.size();
-      std::vector<uint64_t> off(n + 1, 0);
-      std::vector<uint8_t> has(n);
-      HostPool::Get().For(n, 1024, [&](size_t i) {  // prepared feeds, else a view's SetFeed / SetInsert bytes
-        const uint32_t l = fresh[i];
-        const PrepFeed &f = pf_[l];
-        const bool t = !f.has && touched_[l];
-        off[i + 1] = f.has ? f.len + (f.ins ? 4 : 0) : t ? views_[l].feed.size() : 0;
-        has[i] = f.has || (t && views_[l].has_feed);
-      });
-      for (size_t i = 0; i < n; i++) off[i + 1] += off[i];
-      // packed into the part's pinned buffer on all host threads: one DMA
-      if (off[n] > P.pin_cap) {
+      // the chunks' first offsets, then each chunk's lanes packed into the
+      // part's pinned buffer on all host threads: one DMA
+      uint64_t total = 0;
+      for (size_t c = 0; c < chunks; c++) {
+        const uint64_t b = rchunks_[c].bytes;
+        rchunks_[c].bytes = total;
+        total += b;
+      }
+      foff_[n] = total;
+      if (total > P.pin_cap) {
         if (P.pin) wtfgpu_host_free(ctx_, P.pin);
         P.pin = nullptr;
-        P.pin_cap = std::max<uint64_t>(off[n] * 2, 1 << 20);
+        P.pin_cap = std::max<uint64_t>(total * 2, 1 << 20);
         void *p = nullptr;
         if (wtfgpu_host_alloc(ctx_, P.pin_cap, &p)) return false;
         P.pin = (uint8_t *)p;
       }
-      HostPool::Get().For(n, 256, [&](size_t i) {
-        const uint32_t l = fresh[i];
-        const PrepFeed &f = pf_[l];
-        uint8_t *o = P.pin + off[i];
-        if (f.has) {
-          if (f.ins) {
-            memcpy(o, &f.len, 4);
-            o += 4;
+      HostPool::Get().For(chunks, 1, [&](size_t c) {
+        uint64_t at = rchunks_[c].bytes;
+        const size_t hi = std::min(n, (c + 1) * kChunk);
+        for (size_t i = c * kChunk; i < hi; i++) {
+          foff_[i] = at;
+          if (!flen_[i]) continue;
+          const uint32_t l = fresh[i];
+          const PrepFeed &f = pf_[l];
+          uint8_t *o = P.pin + at;
+          if (f.has) {
+            if (f.ins) {
+              memcpy(o, &f.len, 4);
+              o += 4;
+            }
+            if (f.len) memcpy(o, f.p, f.len);
+          } else {
+            memcpy(o, views_[l].feed.data(), flen_[i]);
           }
-          if (f.len) memcpy(o, f.p, f.len);
-        } else if (touched_[l] && !views_[l].feed.empty()) {
-          memcpy(o, views_[l].feed.data(), views_[l].feed.size());
+          at += flen_[i];
         }
-      });
-      if (wtfgpu_set_feed_lanes(ctx_, fresh.data(), (uint32_t)n, off.data(), has.data(), P.pin, off[n]))
+      }, n >= 512);
+      if (wtfgpu_set_feed_lanes(ctx_, fresh.data(), (uint32_t)n, foff_.data(), fhas_.data(), P.pin, total))
         return false;
       stats_.up_feed_ms += ms_since(tf);
     }
-    if (!stop_prestopped(fresh)) return false;
+    // lanes InsertTestcase stopped never run: marked STOPPED on the device, so
+    // the next classification gives them their result
+    if (!pre_.empty() && wtfgpu_stop(ctx_, pre_.data(), (uint32_t)pre_.size(), WTFGPU_EXIT_STOPPED) != WTFGPU_OK)
+      return false;
     stats_.upload_ms += ms_since(tu);
     stats_.testcases += fresh.size();
   }
   stats_.insert_ms += ms_since(ti);
   // ---- one slice over the part's occupied lanes
   const auto to = Clock::now();
-  if (!fresh.empty()) {  // occupied: the lanes still running plus the refilled ones
-    std::vector<uint32_t> occ(P.occ.size() + fresh.size());
-    std::merge(P.occ.begin(), P.occ.end(), fresh.begin(), fresh.end(), occ.begin());
-    P.occ.swap(occ);
+  if (P.occ.empty()) {  // occupied: the lanes still running plus the refilled ones (both ascending)
+    P.occ.swap(fresh);
+  } else if (!fresh.empty()) {
+    tmp_lanes_.resize(P.occ.size() + fresh.size());
+    std::merge(P.occ.begin(), P.occ.end(), fresh.begin(), fresh.end(), tmp_lanes_.begin());
+    P.occ.swap(tmp_lanes_);
   }
   stats_.occ_ms += ms_since(to);
   if (!P.occ.empty()) {
@@ -1682,13 +1759,10 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
   account_run(rs);
   P.launched = false;
   const uint32_t first = P.lo, count = P.hi - P.lo;
-  // the results handed out for these lanes' previous testcases were consumed
-  // before this call: clear them (capacity kept) before this slice's go in
-  HostPool::Get().For(P.occ.size(), 1024, [&](size_t i) {
-    const uint32_t l = P.occ[i];
-    if (!lres_stale_[l]) return;
-    lres_stale_[l] = 0;
-    LaneResult &r = lres_[l];
+  // the results handed out at this part's last harvest were consumed before
+  // this call: cleared (capacity kept) before this slice's go in
+  HostPool::Get().For(P.res_used.size(), 1024, [&](size_t i) {
+    LaneResult &r = lres_[P.res_used[i]];
     r.result = Ok_t();
     r.error = false;
     r.handler_fault = false;
@@ -1696,7 +1770,8 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
     r.icount = 0;
     r.rip = 0;
     r.new_coverage.clear();
-  }, P.occ.size() >= 8192);
+  }, P.res_used.size() >= 8192);
+  P.res_used.clear();
   const bool pf = P.pf;  // the exits (and counts, arguments, coverage count) are in P's pinned buffers
   P.pf = false;
   if (!pf) {
@@ -1711,19 +1786,154 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
     }
     if (wtfgpu_read_exits(ctx_, first, count, P.ex)) return false;
   }
-  std::vector<uint8_t> done(count, 0);
-  std::vector<uint32_t> hits;
-  if (!classify(P.occ, first, P.ex, done, &lres_, hits, pf ? P.sargs : nullptr)) return false;
+  // One pass over the part's occupied lanes, a chunk of them per loop index.
+  // Each lane's exit record is read once: the exit is classified (as
+  // classify does), a finished lane's result written (fill_lane) and its
+  // B_exec bytes added to the chunk's sum. The common exit, Stop(Ok) on a view
+  // the host never touched, gets no LaneResult: the lane is only marked plain
+  // (not when registers are wanted: those results are filled after the pass).
+  // The chunk lists the finished lanes, the ones still running, the
+  // breakpoint hits for the host and the StopWithArgs exits to be named.
+  const wtfgpu_exit_t *ex = P.ex;
+  const size_t n = P.occ.size();
+  constexpr size_t kChunk = 2048;
+  const size_t chunks = (n + kChunk - 1) / kChunk;
+  if (hchunks_.size() < chunks) hchunks_.resize(chunks);
+  const bool fill = !want_gprs_;
+  HostPool::Get().For(chunks, 1, [&](size_t c) {
+    HarvestChunk &C = hchunks_[c];
+    C.fin.clear();
+    C.used.clear();
+    C.run.clear();
+    C.hits.clear();
+    C.named.clear();
+    uint64_t bytes = 0;
+    const size_t hi = std::min(n, (c + 1) * kChunk);
+    for (size_t i = c * kChunk; i < hi; i++) {
+      const uint32_t l = P.occ[i];
+      const wtfgpu_exit_t &e = ex[l - first];
+      // a view the host has not touched since its reset holds no result: the
+      // common exits (Stop(Ok), still running, a breakpoint) leave it so
+      LaneView &v = views_[l];
+      const auto mark = [&]() -> LaneView & {
+        touched_[l] = 1;
+        return v;
+      };
+      bool plain = false, direct = false;
+      // a result the exit alone decides: on a view the host never touched it
+      // goes straight into the lane's LaneResult (the view stays untouched, so
+      // the refill has nothing to reset); else through the view, as classify's
+      const auto ends = [&](TestcaseResult_t &&R) {
+        if (fill && !touched_[l]) {
+          lres_[l].result = std::move(R);
+          direct = true;
+        } else {
+          mark().result = std::move(R);
+        }
+      };
+      switch (e.status) {
+        case WTFGPU_EXIT_BREAKPOINT: C.hits.push_back(l); continue;
+        case WTFGPU_RUNNING: C.run.push_back(l); continue;  // sliced: still running when the slice ended
+        case WTFGPU_EXIT_STOP_ARGS: C.named.push_back(l); continue;
+        case WTFGPU_EXIT_TIMEOUT: ends(Timedout_t()); break;
+        case WTFGPU_EXIT_INT3:
+        case WTFGPU_EXIT_HLT: ends(Crash_t()); break;
+        case WTFGPU_EXIT_CR3: ends(Cr3Change_t()); break;
+        case WTFGPU_EXIT_FAULT: ends(FaultToResult(e.vector, e.error, e.rip, e.addr, e.opcode)); break;
+        case WTFGPU_EXIT_STOPPED: break;
+        case WTFGPU_EXIT_STOP_OK:  // device Feed action: Stop(Ok_t()) (an untouched view reads as Ok already)
+          if (touched_[l])
+            v.result = Ok_t();
+          else
+            plain = fill;
+          break;
+        case WTFGPU_EXIT_FEED_FAULT: mark().handler_fault = true; break;  // U43: fill_lane makes it an engine error
+        default:  // the engine cannot finish the testcase (see classify)
+          lres_[l].error = true;
+          if (!v.result) mark().result = Crash_t();
+          if (e.status == WTFGPU_EXIT_UNIMPLEMENTED) {
+            stats_.err_unimpl++;
+            stats_.unimpl_ops.add(e.opcode);
+            stats_.last_unimpl_op = e.opcode;
+            stats_.last_unimpl_rip = e.rip;
+          } else if (e.status == WTFGPU_EXIT_OVERLAY_FULL) {
+            stats_.err_overlay++;
+          } else {
+            stats_.err_other++;
+          }
+          break;
+      }
+      C.fin.push_back(l);
+      if (plain) {
+        plain_[l] = 1;
+      } else {
+        C.used.push_back(l);
+        if (direct) {  // as fill_lane on an untouched view, the result in place already
+          LaneResult &r = lres_[l];
+          r.rip = e.rip;
+          r.icount = e.icount;
+          r.exit_status = e.status;
+        } else if (fill) {
+          fill_lane(l, e, lres_[l]);
+        }
+      }
+      // B_exec = instruction + data bytes, testcase bytes, 2 x 4096 per dirty page
+      if (pf) bytes += P.nb[l - first] + 2ull * 4096 * P.dc[l - first] + tc_bytes_[l];
+    }
+    C.bytes = bytes;
+  }, n >= 2048);
+  // the chunks' lists in chunk order: ascending
+  std::vector<uint32_t> &finished = fin_;
+  finished.clear();
+  run_.clear();
+  hits_.clear();
+  named_.clear();
+  uint64_t b_exec = 0;
+  for (size_t c = 0; c < chunks; c++) {
+    const HarvestChunk &C = hchunks_[c];
+    finished.insert(finished.end(), C.fin.begin(), C.fin.end());
+    P.res_used.insert(P.res_used.end(), C.used.begin(), C.used.end());
+    run_.insert(run_.end(), C.run.begin(), C.run.end());
+    hits_.insert(hits_.end(), C.hits.begin(), C.hits.end());
+    named_.insert(named_.end(), C.named.begin(), C.named.end());
+    b_exec += C.bytes;
+  }
+  name_stop_args(named_, first, ex, done_, &lres_, pf ? P.sargs : nullptr);
   stats_.exits_ms += ms_since(te);
-  if (!hits.empty() && !service_hits(hits, first, done, Slots, Slots != nullptr)) return false;
-  std::vector<uint32_t> finished;
-  if (!fill_results(P.occ, first, P.ex, done, &lres_, &finished)) return false;
+  if (!hits_.empty() && !service_hits(hits_, first, done_, Slots, Slots != nullptr)) return false;
+  if (!hits_.empty() || !named_.empty()) {
+    // the lanes the host named or serviced, in lane order: the finished ones
+    // join the finished list, the others stay occupied
+    late_.resize(hits_.size() + named_.size());
+    std::merge(hits_.begin(), hits_.end(), named_.begin(), named_.end(), late_.begin());
+    std::vector<uint32_t> late_fin, late_run;
+    for (uint32_t l : late_) {
+      (done_[l - first] ? late_fin : late_run).push_back(l);
+      done_[l - first] = 0;
+    }
+    if (fill) {
+      HostPool::Get().For(late_fin.size(), 1024, [&](size_t i) {
+        fill_lane(late_fin[i], ex[late_fin[i] - first], lres_[late_fin[i]]);
+      }, late_fin.size() >= 2048);
+    }
+    if (pf)
+      for (uint32_t l : late_fin) b_exec += P.nb[l - first] + 2ull * 4096 * P.dc[l - first] + tc_bytes_[l];
+    const auto join = [&](std::vector<uint32_t> &into, const std::vector<uint32_t> &add) {
+      if (add.empty()) return;
+      tmp_lanes_.resize(into.size() + add.size());
+      std::merge(into.begin(), into.end(), add.begin(), add.end(), tmp_lanes_.begin());
+      into.swap(tmp_lanes_);
+    };
+    join(finished, late_fin);
+    join(P.res_used, late_fin);
+    join(run_, late_run);
+  }
+  P.occ.swap(run_);  // the lanes still occupied
   if (finished.empty()) return true;
+  if (!fill && !fill_lanes(finished, first, ex, lres_)) return false;
   const auto tc = Clock::now();
-  if (pf) {  // B_exec = instruction + data bytes, testcase bytes, 2 x 4096 per dirty page
-    uint64_t b = 0;
-    for (uint32_t l : finished) b += P.nb[l - first] + 2ull * 4096 * P.dc[l - first] + tc_bytes_[l];
-    stats_.alg_bytes += b;
+  if (pf) {
+    stats_.alg_bytes += b_exec;
   } else {
     uint32_t lo = finished.front() & ~63u, hi = finished.back() + 1;
     std::vector<uint64_t> nb(hi - lo);
@@ -1734,6 +1944,21 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
   }
   stats_.bytes_ms += ms_since(tc);
   collect_coverage(finished, lres_, pf && P.pf_cov ? P.cov_hdr : nullptr);
+  {  // a plain lane that reported new coverage gets its LaneResult after all (entries sorted by lane)
+    uint32_t last = ~0u;
+    size_t added = 0;
+    for (const std::pair<uint32_t, uint64_t> &E : cov_sorted_) {
+      const uint32_t l = E.first;
+      if (l == last) continue;
+      last = l;
+      if (!plain_[l] || lres_[l].new_coverage.empty()) continue;
+      plain_[l] = 0;
+      fill_lane(l, ex[l - first], lres_[l]);
+      P.res_used.push_back(l);
+      added++;
+    }
+    if (added) std::inplace_merge(P.res_used.begin(), P.res_used.end() - (std::ptrdiff_t)added, P.res_used.end());
+  }
   const auto tr = Clock::now();
   stats_.coverage_ms += std::chrono::duration<double, std::milli>(tr - tc).count();
   target_restore(Target, finished, Slots);
@@ -1741,18 +1966,23 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
   const auto tout = Clock::now();
   const size_t base = Out.size();
   Out.resize(base + finished.size());
-  for (size_t i = 0; i < finished.size(); i++) {
+  HostPool::Get().For(finished.size(), 2048, [&](size_t i) {
     const uint32_t l = finished[i];
-    Out[base + i] = StreamResult_t{tag_[l], &lres_[l]};
+    if (plain_[l]) {
+      plain_[l] = 0;
+      Out[base + i] = StreamResult_t{tag_[l], nullptr, ex[l - first].icount};
+    } else {
+      Out[base + i] = StreamResult_t{tag_[l], &lres_[l]};
+    }
     busy_[l] = 0;  // not runnable until refilled (a finished lane keeps its exit status)
-  }
-  {  // the finished lanes leave the occupied list for the free one (all ascending)
-    std::vector<uint32_t> occ(P.occ.size()), fr(P.free.size() + finished.size());
-    occ.resize(std::set_difference(P.occ.begin(), P.occ.end(), finished.begin(), finished.end(), occ.begin()) -
-               occ.begin());
-    std::merge(P.free.begin(), P.free.end(), finished.begin(), finished.end(), fr.begin());
-    P.occ.swap(occ);
-    P.free.swap(fr);
+  }, finished.size() >= 8192);
+  // the finished lanes join the free ones (both ascending)
+  if (P.free.empty()) {
+    P.free.swap(finished);
+  } else {
+    tmp_lanes_.resize(P.free.size() + finished.size());
+    std::merge(P.free.begin(), P.free.end(), finished.begin(), finished.end(), tmp_lanes_.begin());
+    P.free.swap(tmp_lanes_);
   }
   stats_.out_ms += ms_since(tout);
   stats_.batches++;

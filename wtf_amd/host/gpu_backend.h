@@ -221,8 +221,16 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   bool classify(const std::vector<uint32_t> &pending, uint32_t first, const wtfgpu_exit_t *ex,
                 std::vector<uint8_t> &done, std::vector<LaneResult> *out, std::vector<uint32_t> &hits,
                 const uint64_t *stop_args = nullptr);
+  // the device StopWithArgs exits of `named`: each lane's result from the kept arguments
+  void name_stop_args(const std::vector<uint32_t> &named, uint32_t first, const wtfgpu_exit_t *ex,
+                      std::vector<uint8_t> &done, std::vector<LaneResult> *out, const uint64_t *stop_args);
   bool fill_results(const std::vector<uint32_t> &lanes, uint32_t first, const wtfgpu_exit_t *ex,
                     const std::vector<uint8_t> &done, std::vector<LaneResult> *out, std::vector<uint32_t> *finished);
+  // the final state of the finished lanes `fin` (registers and run stats read when wanted)
+  bool fill_lanes(const std::vector<uint32_t> &fin, uint32_t first, const wtfgpu_exit_t *ex,
+                  std::vector<LaneResult> &out);
+  // one finished lane's result, exit status, rip and retired count from its view and exit record
+  void fill_lane(uint32_t l, const wtfgpu_exit_t &e, LaneResult &r);
   bool stop_prestopped(const std::vector<uint32_t> &lanes);
   void account_run(const wtfgpu_run_stats_t &rs);
   bool service_hits(const std::vector<uint32_t> &hits, uint32_t first, std::vector<uint8_t> &done, ModuleSlots *slots,
@@ -242,8 +250,33 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   std::vector<uint8_t> busy_;
   std::vector<uint64_t> tag_;
   std::vector<uint64_t> tc_bytes_;  // the testcase size in each lane (B_exec)
+  // lres_[l] is in its cleared state (Ok, no error, no coverage) unless the
+  // lane is in its part's res_used list
   std::vector<LaneResult> lres_;
-  std::vector<uint8_t> lres_stale_;  // lres_[l] still holds a handed-out result: reset at the lane's next harvest
+  // lanes that finished with the common result (Stop(Ok), view untouched): no
+  // LaneResult is written for them unless they report new coverage
+  std::vector<uint8_t> plain_;
+  std::vector<uint8_t> done_;  // service_hits' flags of a part's lanes; all zero between harvests
+  // The harvest pass's output per chunk of a part's occupied lanes, each list
+  // ascending; the chunks' lists concatenated in chunk order are ascending too.
+  struct HarvestChunk {
+    std::vector<uint32_t> fin, used, run, hits, named;  // finished (used: those with a LaneResult), still running, ...
+    uint64_t bytes = 0;                                 // B_exec of fin
+  };
+  std::vector<HarvestChunk> hchunks_;
+  std::vector<uint32_t> hits_, named_, late_, fin_, run_, tmp_lanes_;  // harvest lists, kept for their capacity
+  // The refill pass's output per chunk of the fresh lanes: lanes whose
+  // InsertTestcase is still to be called (indices into the fresh list), lanes
+  // that hold a result before they ran, the chunk's feed bytes
+  struct RefillChunk {
+    std::vector<uint32_t> call, pre;
+    uint64_t bytes = 0;
+  };
+  std::vector<RefillChunk> rchunks_;
+  std::vector<uint32_t> fresh_, call_, pre_;
+  std::vector<uint32_t> flen_;  // feed bytes of each fresh lane
+  std::vector<uint64_t> foff_;  // their offsets in the part's pinned buffer (prefix sum of flen_)
+  std::vector<uint8_t> fhas_;   // the lane has a feed for the device
   std::vector<uint32_t> cov_lanes_;  // coverage collection buffers (streaming)
   std::vector<uint64_t> cov_rips_;
   std::vector<uint8_t> cov_want_;  // lanes whose prefetched entries count (collect_coverage)
@@ -261,6 +294,7 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
     // the part's occupied and free lanes, ascending, kept as lanes finish and
     // are refilled (the refill takes the lowest free lanes first)
     std::vector<uint32_t> occ, free;
+    std::vector<uint32_t> res_used;  // lanes whose lres_ entry the last harvest handed out: cleared at the next
     wtfgpu_exit_t *ex = nullptr;  // the slice's exit records: pinned (one DMA of 40 B per lane)
     uint64_t ex_cap = 0;
     uint8_t *pin = nullptr;

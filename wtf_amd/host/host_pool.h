@@ -1,8 +1,8 @@
 // host_pool.h — the node's host worker pool (per-lane loops of the gpu
 // backend: uploads, exit classification, module calls, harvests).
 //
-// The batch mutator runs on its own threads at the same time as these loops
-// (runner.cc MakeBatch), so idle pool workers must give their core back
+// The batch mutator runs on a second pool of this class at the same time as
+// these loops (runner.cc MutatePool), so idle pool workers must give their core back
 // quickly: each worker spins briefly (kSpin pause iterations, a few
 // microseconds) for the next loop, then sleeps on a condition variable.
 // (OpenMP's default wait policy spins for milliseconds after every parallel

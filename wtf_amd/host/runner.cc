@@ -25,6 +25,17 @@ namespace {
 // parallel mutation of a fuzz batch (make_batch): batches of at least
 // kParMutateMin new testcases, kMutateChunk testcases per generator
 constexpr size_t kParMutateMin = 8192, kMutateChunk = 2048;
+// The threads that mutate a batch's chunks: a pool of its own, created at the
+// first large batch (the step thread's loops hold HostPool::Get() while the
+// next batch is made). host_threads() of them, or WTF_MUTATE_THREADS for
+// A/Bs; the chunks make the batch the same whatever the count.
+HostPool &MutatePool() {
+  static HostPool P([] {
+    const char *e = getenv("WTF_MUTATE_THREADS");
+    return e && atoi(e) > 0 ? (unsigned)atoi(e) : host_threads();
+  }());
+  return P;
+}
 // CPU time of the calling thread (ns)
 uint64_t ThreadCpuNs() {
   timespec t{};
@@ -692,7 +703,7 @@ bool FuzzSession::Start() {
     Prepare_ = Target_.PrepareInsert;
   if (stream_) {
     Adopt(MakeBatch(Budget(Exec_.Lanes())));
-    return !Ready_.empty();
+    return ReadyCount_ != 0;
   }
   Batch_ = MakeBatch(Budget(Exec_.Lanes()));
   return !Batch_.empty();
@@ -702,7 +713,8 @@ void FuzzSession::Adopt(TcBatch &&B) {
   for (std::unique_ptr<TcArena> &A : B) {
     if (!A || A->Count() == 0) continue;
     A->Live = A->Count();
-    for (size_t i = 0; i < A->Count(); i++) Ready_.push_back(TcRef{A.get(), (uint32_t)i});
+    Ready_.push_back(TcRange{A.get(), 0, (uint32_t)A->Count()});
+    ReadyCount_ += A->Count();
     TcArena *K = A.get();
     Arenas_.emplace(K, std::move(A));
   }
@@ -711,14 +723,14 @@ void FuzzSession::Adopt(TcBatch &&B) {
 // at most n more testcases within the --runs budget
 uint64_t FuzzSession::Budget(uint64_t n) const {
   if (!O_.runs) return n;
-  const uint64_t made = S_.execs + (stream_ ? InFlight_ + Ready_.size() : 0);
+  const uint64_t made = S_.execs + (stream_ ? InFlight_ + ReadyCount_ : 0);
   return made >= O_.runs ? 0 : std::min<uint64_t>(n, O_.runs - made);
 }
 
 bool FuzzSession::Done() const {
   if (!stream_) return Batch_.empty();
   if (O_.seconds > 0 && secs_since(t0_) >= O_.seconds) return true;  // in-flight testcases are dropped
-  return Ready_.empty() && InFlight_ == 0 && !Next_.valid() &&
+  return ReadyCount_ == 0 && InFlight_ == 0 && !Next_.valid() &&
          (Budget(1) == 0 || !More(S_.execs) || Corpus_.Size() == 0);
 }
 
@@ -751,11 +763,12 @@ TcBatch FuzzSession::MakeBatch(uint64_t n) {
     std::vector<uint64_t> Seeds(Chunks);
     for (uint64_t &S : Seeds) S = Rng_();
     std::vector<std::unique_ptr<TcArena>> Out(Chunks);
-    std::atomic<size_t> NextChunk{0};
     std::atomic<uint64_t> CpuNs{0};
-    auto Work = [&]() {
+    // on the mutation pool's threads, created once (the step thread's loops
+    // run on HostPool::Get() at the same time)
+    MutatePool().For(Chunks, 1, [&](size_t c) {
       const uint64_t c0 = ThreadCpuNs();
-      for (size_t c; (c = NextChunk.fetch_add(1)) < Chunks;) {
+      {
         std::mt19937_64 R(Seeds[c]);
         Corpus_t View(Corpus_, R);
         std::unique_ptr<Mutator_t> M = Target_.CreateMutator(R, O_.max_len);
@@ -774,17 +787,7 @@ TcBatch FuzzSession::MakeBatch(uint64_t n) {
         Out[c] = std::move(A);
       }
       CpuNs += ThreadCpuNs() - c0;
-    };
-    std::vector<std::thread> Pool;
-    // (WTF_MUTATE_THREADS: the threads mutating, for A/Bs; the chunks make the
-    // batch the same whatever the count)
-    static const unsigned MutThreads = [] {
-      const char *e = getenv("WTF_MUTATE_THREADS");
-      return e && atoi(e) > 0 ? (unsigned)atoi(e) : host_threads();
-    }();
-    for (unsigned t = 1; t < MutThreads; t++) Pool.emplace_back(Work);
-    Work();
-    for (std::thread &Th : Pool) Th.join();
+    });
     MutateCpuNs_ += CpuNs.load();
     for (std::unique_ptr<TcArena> &A : Out) Batch.push_back(std::move(A));
     Made += Need;
@@ -866,45 +869,72 @@ bool FuzzSession::Step() {
 bool FuzzSession::StreamStep(bool Done) {
   if (Done) return true;
   const auto t_step = Clock::now();
-  std::vector<StreamTestcase_t> In;
+  // (resized, not cleared: every element up to `take` is written below, and
+  // most steps take as many as the last one did)
+  std::vector<StreamTestcase_t> &In = In_;
   const bool open = More(S_.execs);
+  if (!open) In.clear();
   if (open) {
     const uint32_t free = Exec_.FreeLanes();
-    if (Ready_.size() < free && !Next_.valid() && Corpus_.Size()) {  // nothing in the pipe: make them now
+    if (ReadyCount_ < free && !Next_.valid() && Corpus_.Size()) {  // nothing in the pipe: make them now
       const auto tm = Clock::now();
-      Adopt(MakeBatch(Budget(free - Ready_.size())));
+      Adopt(MakeBatch(Budget(free - ReadyCount_)));
       S_.make_ms += secs_since(tm) * 1e3;
     }
-    // the next `take` ready testcases, each in a free slot (its tag): taken in
-    // bulk, the slots and the executor's descriptors filled on all host threads
-    const size_t take = std::min<size_t>(free, Ready_.size());
+    // the next `take` ready testcases, each in a free slot (its tag): taken as
+    // arena ranges, the slots and the executor's descriptors filled on all
+    // host threads, one chunk of kFill testcases per loop index
+    const size_t take = std::min<size_t>(free, ReadyCount_);
     while (FreeSlot_.size() < take) {
       FreeSlot_.push_back(Slot_.size());
       Slot_.emplace_back();
     }
     const size_t base = FreeSlot_.size() - take;
-    std::vector<TcRef> Refs(Ready_.begin(), Ready_.begin() + (std::ptrdiff_t)take);
-    Ready_.erase(Ready_.begin(), Ready_.begin() + (std::ptrdiff_t)take);
+    Taken_.clear();
+    for (size_t got = 0; got < take;) {
+      TcRange &F = Ready_.front();
+      const uint32_t k = (uint32_t)std::min<size_t>(F.E - F.B, take - got);
+      Taken_.push_back({TcRange{F.A, F.B, F.B + k}, got});
+      got += k;
+      F.B += k;
+      if (F.B == F.E) Ready_.pop_front();
+    }
+    ReadyCount_ -= take;
     In.resize(take);
-    HostPool::Get().For(take, 1024, [&](size_t i) {
-      const uint64_t tag = FreeSlot_[base + i];
-      const TcRef R = Refs[i];
-      Slot_[tag] = R;
-      StreamTestcase_t T{R.data(), R.size(), tag};
-      if (R.A->Prep.size() == R.A->Count()) {
-        T.prep = R.prep();
-        T.prep_data = R.prep_data();
-        T.prep_size = R.prep_size();
+    constexpr size_t kFill = 1024;
+    HostPool::Get().For((take + kFill - 1) / kFill, 1, [&](size_t c) {
+      const size_t lo = c * kFill, hi = std::min(take, lo + kFill);
+      // the range that holds testcase lo: the last one starting at or before it
+      size_t r = (size_t)(std::upper_bound(Taken_.begin(), Taken_.end(), lo,
+                                           [](size_t v, const std::pair<TcRange, size_t> &T) { return v < T.second; }) -
+                          Taken_.begin()) - 1;
+      for (size_t i = lo; i < hi; r++) {
+        const TcRange &G = Taken_[r].first;
+        TcArena *A = G.A;
+        const bool prep = A->Prep.size() == A->Count();
+        const size_t end = std::min<size_t>(hi, Taken_[r].second + (G.E - G.B));
+        for (; i < end; i++) {
+          const uint64_t tag = FreeSlot_[base + i];
+          const TcRef R{A, G.B + (uint32_t)(i - Taken_[r].second)};
+          Slot_[tag] = R;
+          StreamTestcase_t T{R.data(), R.size(), tag};
+          if (prep) {
+            T.prep = R.prep();
+            T.prep_data = R.prep_data();
+            T.prep_size = R.prep_size();
+          }
+          In[i] = T;
+        }
       }
-      In[i] = T;
     }, take >= 4096);
     FreeSlot_.resize(base);
     InFlight_ += take;
-    const uint64_t want = Budget(Exec_.Lanes() > Ready_.size() ? Exec_.Lanes() - Ready_.size() : 0);
+    const uint64_t want = Budget(Exec_.Lanes() > ReadyCount_ ? Exec_.Lanes() - ReadyCount_ : 0);
     if (want && Corpus_.Size() && !Next_.valid())
       Next_ = std::async(std::launch::async, &FuzzSession::MakeBatch, this, want);
   }
-  std::vector<StreamResult_t> Out;
+  std::vector<StreamResult_t> &Out = Out_;
+  Out.clear();
   const auto tb = Clock::now();
   S_.fill_ms += std::chrono::duration<double, std::milli>(tb - t_step).count();
   size_t Taken = 0;
@@ -912,7 +942,12 @@ bool FuzzSession::StreamStep(bool Done) {
   S_.run_s += secs_since(tb);
   // testcases the executor did not take go back to the front of the queue
   for (size_t i = In.size(); i-- > Taken;) {
-    Ready_.push_front(Slot_[In[i].tag]);
+    const TcRef R = Slot_[In[i].tag];
+    if (!Ready_.empty() && Ready_.front().A == R.A && Ready_.front().B == R.I + 1)
+      Ready_.front().B = R.I;
+    else
+      Ready_.push_front(TcRange{R.A, R.I, R.I + 1});
+    ReadyCount_++;
     Slot_[In[i].tag] = TcRef{};
     FreeSlot_.push_back(In[i].tag);
     InFlight_--;
@@ -923,9 +958,7 @@ bool FuzzSession::StreamStep(bool Done) {
   S_.produce_wait_ms += std::chrono::duration<double, std::milli>(ta - tw).count();
   if (!ok) return false;
   S_.batches++;
-  for (const StreamResult_t &F : Out)
-    if (F.tag >= Slot_.size()) return false;
-  AccountStep(Out);
+  if (!AccountStep(Out)) return false;
   S_.account_ms += secs_since(ta) * 1e3;
   if (X_ && X_->Exchanging() && !MergeCoverage(false)) return false;
   S_.step_ms += secs_since(t_step) * 1e3;
@@ -964,75 +997,90 @@ void FuzzSession::ReleaseArena(TcArena *A) {
 // results whose bookkeeping depends on the order (engine errors kept as files,
 // crash names not seen yet, new coverage) go through Account one by one. The
 // results' slots are freed and their arenas released in bulk.
-void FuzzSession::AccountStep(std::vector<StreamResult_t> &Out) {
+bool FuzzSession::AccountStep(std::vector<StreamResult_t> &Out) {
   const size_t n = Out.size();
   enum : uint8_t { K_SERIAL = 1, K_TIMEOUT = 2, K_CR3 = 4, K_CRASH = 8 };
-  std::vector<uint8_t> Kind(n, 0);
-  std::vector<TcArena *> Ar(n);
-  struct Sum {
-    uint64_t retired = 0, timeouts = 0, cr3 = 0, crashes = 0;
-  };
-  const unsigned T = HostPool::Get().Threads();
-  std::vector<Sum> Part(T + 1);
+  constexpr size_t kChunk = 2048;
+  const size_t chunks = (n + kChunk - 1) / kChunk;
+  if (Acct_.size() < chunks) Acct_.resize(chunks);
   const bool every = Sample_ != nullptr;  // samples follow the accounting order: all of it serial
-  HostPool::Get().For(n, 1024, [&](size_t i) {
-    const LaneResult &L = *Out[i].r;
-    const TcRef R = Slot_[Out[i].tag];
-    Ar[i] = R.A;
-    uint8_t k = 0;
-    if (every || L.error) {
-      k = K_SERIAL;
-    } else {
-      if (std::holds_alternative<Timedout_t>(L.result)) k |= K_TIMEOUT;
-      if (std::holds_alternative<Cr3Change_t>(L.result)) k |= K_CR3;
-      if (const Crash_t *C = std::get_if<Crash_t>(&L.result)) {
-        k |= K_CRASH;
-        if (!C->CrashName.empty() && !CrashNames_.count(C->CrashName)) k = K_SERIAL;  // a new name
+  const size_t fs = FreeSlot_.size(), slots = Slot_.size();
+  FreeSlot_.resize(fs + n);
+  std::atomic<bool> bad{false};
+  // one pass: the result's kind and counts, its slot back, its arena's run
+  HostPool::Get().For(chunks, 1, [&](size_t c) {
+    AcctChunk &C = Acct_[c];
+    C.retired = C.timeouts = C.cr3 = C.crashes = 0;
+    C.serial.clear();
+    C.arena.clear();
+    const size_t hi = std::min(n, (c + 1) * kChunk);
+    for (size_t i = c * kChunk; i < hi; i++) {
+      const uint64_t tag = Out[i].tag;
+      if (tag >= slots) {  // not a tag this session gave out
+        bad = true;
+        FreeSlot_[fs + i] = 0;
+        continue;
       }
-      if (!L.new_coverage.empty() && !std::holds_alternative<Timedout_t>(L.result)) k = K_SERIAL;
-    }
-    Kind[i] = k;
-    if (k != K_SERIAL) {
-      Sum &s = Part[HostPool::ThreadIndex()];
-      s.retired += L.icount;
-      s.timeouts += (k & K_TIMEOUT) != 0;
-      s.cr3 += (k & K_CR3) != 0;
-      s.crashes += (k & K_CRASH) != 0;
+      const TcRef R = Slot_[tag];
+      Slot_[tag] = TcRef{};
+      FreeSlot_[fs + i] = tag;
+      if (!C.arena.empty() && C.arena.back().first == R.A)
+        C.arena.back().second++;
+      else
+        C.arena.push_back({R.A, 1});
+      const LaneResult *L = Out[i].r;
+      if (!L && !every) {  // the common result, as a count
+        C.retired += Out[i].icount;
+        continue;
+      }
+      uint8_t k = 0;
+      if (every || L->error) {
+        k = K_SERIAL;
+      } else {
+        if (std::holds_alternative<Timedout_t>(L->result)) k |= K_TIMEOUT;
+        if (std::holds_alternative<Cr3Change_t>(L->result)) k |= K_CR3;
+        if (const Crash_t *Cr = std::get_if<Crash_t>(&L->result)) {
+          k |= K_CRASH;
+          if (!Cr->CrashName.empty() && !CrashNames_.count(Cr->CrashName)) k = K_SERIAL;  // a new name
+        }
+        if (!L->new_coverage.empty() && !std::holds_alternative<Timedout_t>(L->result)) k = K_SERIAL;
+      }
+      if (k == K_SERIAL) {
+        C.serial.push_back({(uint32_t)i, R});
+        continue;
+      }
+      C.retired += L->icount;
+      C.timeouts += (k & K_TIMEOUT) != 0;
+      C.cr3 += (k & K_CR3) != 0;
+      C.crashes += (k & K_CRASH) != 0;
     }
   }, n >= 4096);
+  if (bad) return false;
   // the order-dependent results, in order (counts included: Account adds them)
-  uint64_t bulk = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (Kind[i] != K_SERIAL) {
-      bulk++;
-      continue;
+  uint64_t serial = 0;
+  LaneResult Plain;  // a counted result that --sample sends through Account
+  for (size_t c = 0; c < chunks; c++)
+    for (const std::pair<uint32_t, TcRef> &E : Acct_[c].serial) {
+      const StreamResult_t &F = Out[E.first];
+      serial++;
+      if (!F.r) Plain.icount = F.icount;
+      Account(E.second.data(), E.second.size(), F.r ? *F.r : Plain, false);
     }
-    const TcRef R = Slot_[Out[i].tag];
-    Account(R.data(), R.size(), *Out[i].r, false);
-  }
-  S_.execs += bulk;
-  for (const Sum &s : Part) {
-    S_.retired += s.retired;
-    S_.timeouts += s.timeouts;
-    S_.cr3 += s.cr3;
-    S_.crashes += s.crashes;
-  }
-  // slots back, arenas whose testcases are all accounted released (runs of one arena)
-  const size_t fs = FreeSlot_.size();
-  FreeSlot_.resize(fs + n);
-  HostPool::Get().For(n, 4096, [&](size_t i) {
-    Slot_[Out[i].tag] = TcRef{};
-    FreeSlot_[fs + i] = Out[i].tag;
-  }, n >= 8192);
+  S_.execs += n - serial;
   InFlight_ -= n;
-  for (size_t i = 0; i < n;) {
-    size_t j = i + 1;
-    while (j < n && Ar[j] == Ar[i]) j++;
-    TcArena *A = Ar[i];
-    A->Live -= j - i;
-    if (A->Live == 0) ReleaseArena(A);  // every testcase of the arena accounted
-    i = j;
+  for (size_t c = 0; c < chunks; c++) {
+    const AcctChunk &C = Acct_[c];
+    S_.retired += C.retired;
+    S_.timeouts += C.timeouts;
+    S_.cr3 += C.cr3;
+    S_.crashes += C.crashes;
+    // arenas whose testcases are all accounted are released
+    for (const std::pair<TcArena *, uint32_t> &E : C.arena) {
+      E.first->Live -= E.second;
+      if (E.first->Live == 0) ReleaseArena(E.first);
+    }
   }
+  return true;
 }
 
 // The master's bookkeeping of one result (server.h:816-886).

@@ -55,9 +55,13 @@ struct StreamTestcase_t {
 // A finished testcase: its tag and its result, which stays in the executor's
 // storage and is valid until the executor's next StreamStep (no per-result
 // copies of the ~250-byte LaneResult on the step's thread).
+// r == nullptr: the common result as a count, no LaneResult behind it: Ok_t,
+// no engine error, no new coverage, `icount` instructions retired (only from
+// an executor that was not asked for registers, SetWantRegisters(false)).
 struct StreamResult_t {
   uint64_t tag;
   LaneResult *r;
+  uint64_t icount = 0;  // with r == nullptr
 };
 
 // A backend that runs many testcases per call (GpuBackend_t; the oracle twin
@@ -347,7 +351,7 @@ class FuzzSession {
   FILE *Sample_ = nullptr;
   bool StreamStep(bool Done);
   void Account(const uint8_t *Tc, size_t Size, const LaneResult &L, bool KnownCrash = false);
-  void AccountStep(std::vector<StreamResult_t> &Out);
+  bool AccountStep(std::vector<StreamResult_t> &Out);  // false: a result carries a tag this session never gave out
   // arenas: a released one (every testcase accounted) is kept for the next
   // batch (its buffers keep their capacity: no allocation and no first-touch
   // page faults per batch)
@@ -378,11 +382,30 @@ class FuzzSession {
   std::chrono::steady_clock::time_point t0_;
   // streaming (RunnerOptions::slice != 0 on an executor that streams)
   bool stream_ = false;
-  std::deque<TcRef> Ready_;                                      // mutated, not yet in a lane
+  // mutated, not yet in a lane: testcases [B, E) of an arena, in queue order
+  struct TcRange {
+    TcArena *A = nullptr;
+    uint32_t B = 0, E = 0;
+  };
+  std::deque<TcRange> Ready_;
+  size_t ReadyCount_ = 0;                                           // testcases in Ready_
   std::unordered_map<TcArena *, std::unique_ptr<TcArena>> Arenas_;  // owners of Ready_ / Slot_ testcases
   std::vector<TcRef> Slot_;  // tag -> testcase in a lane (tags are slot indices)
   std::vector<uint64_t> FreeSlot_;
   size_t InFlight_ = 0;
+  // per-step buffers, kept for their capacity: the step's testcases and
+  // results, the ranges taken from Ready_ with each one's first index in In_
+  std::vector<StreamTestcase_t> In_;
+  std::vector<StreamResult_t> Out_;
+  std::vector<std::pair<TcRange, size_t>> Taken_;
+  // AccountStep: one chunk of results per loop index; what depends on the
+  // order comes out of the pass as short per-chunk lists, read in chunk order
+  struct AcctChunk {
+    uint64_t retired = 0, timeouts = 0, cr3 = 0, crashes = 0;
+    std::vector<std::pair<uint32_t, TcRef>> serial;     // results that go through Account, by index
+    std::vector<std::pair<TcArena *, uint32_t>> arena;  // runs of one arena: how many of its testcases
+  };
+  std::vector<AcctChunk> Acct_;
 };
 
 bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O);
