@@ -1,0 +1,508 @@
+"""Grouped execution in k_run vs the CPU oracle: many lanes on few programs.
+
+tests/test_gpu_progfuzz.py gives every lane a program of its own, so a wave
+never holds two lanes at one rip and every group of the wave-level interpreter
+has one lane. Here 512 lanes share 16 programs (progfuzz.build_shared: lane i
+runs program (i // 4) % 16, registers / flags / XMM state per lane), and the
+programs derive per-lane effective addresses from that state. Per lane, bit
+exact against the oracle: exit status / vector / error / address, rip, retired
+count, the 16 GPRs, RFLAGS, the coverage set, the dirty set, the byte counter,
+with sse the XMM / YMM-high / MXCSR state, and for every 8th lane the contents
+of the data window and the stack. tests/test_progfuzz_shared.py holds the
+generator to the divergence this needs.
+
+Which group hazards each test reaches (engine_run.h, k_run):
+
+  test_grouped_run_matches_oracle        default launch. Min-rip selection with
+      several groups in a wave; the ingm mask (lanes of a group on different
+      code-page copies); the round-based fast path with some lanes of a group
+      missing (TLB miss, first write) while the others retire; fast_fault in a
+      part of a group (#PF on the read-only page, #GP of a misaligned SSE
+      operand, #XM, #DE) while the rest goes on; page-crossing operands in a
+      part of a group (slow step for those lanes); the wave-cooperative
+      copy-on-write with several lanes making their first write at once, to
+      the same guest page or to different ones; per-position `logged` bits
+      (lanes of a group reaching a rip the others have logged already); the
+      regrouping permutation between launches (default schedule of a run to
+      completion). Asserts that groups really formed: more than 2 lanes
+      retired per wave-step.
+  test_launch_shapes_match_oracle        the same under every launch shape:
+      fixed lane order (one launch, no permutation); regrouping forced every
+      64 wave-steps (store_lane / load_lane and the permutation many times,
+      lanes of a group change wave and position); host-sliced runs of 5 and 64
+      wave-steps (launch boundaries inside loops, rep strings and groups; the
+      warm LDS image carried from launch to launch); async slices; 32 and 16
+      lanes per wave (the lane / position mapping, waves with idle positions);
+      a cold LDS uop cache at every launch; no shared uop cache (every decode
+      by the wave itself); hot caches (a second pass over warm LDS images and
+      a filled shared cache); a coverage map over the code pages (the
+      covered-flag lookups, nothing committed); and forced regrouping +
+      slices + 16 lanes per wave together on the floating-point seed.
+  test_slice_length_is_path_independent  the U44 claim of k_run: what a lane
+      has done after each 64 wave-step slice does not depend on which path
+      served a group (warm or cold LDS cache, shared cache or own decode,
+      covered or uncovered rips: the `logged` / UC_COVERED paths).
+  test_breakpoints_with_mixed_skip_groups  host breakpoints at block heads,
+      also inside counted loops and at jcc targets; lanes stop, are checked
+      against the oracle's stop list and resumed with skip, every other one a
+      round later, so that resumed and freshly arriving lanes meet at one
+      breakpoint rip in one group (`ingm & ~__ballot(skip)`): asserted to have
+      happened. Once in fixed order, once with forced regrouping (lflags
+      travel with the lane through the permutation).
+
+Observed on MI355X, lanes retired per wave-step with default settings (the
+test asserts > 2.0, the non-degeneracy bound; with a program per lane the
+figure cannot exceed 1.0): seed 31: 30.4, seed 32: 29.6, seed 35 (sse): 24.2,
+seed 34 (sse, fp): 30.2, each in 4 launches. The default run to completion
+regroups, which brings the 32 lanes of a program side by side, and the
+programs that run into the instruction limit do so in lockstep; both push the
+figure far above the 4 lanes of a program that a wave holds in lane order.
+Stops of a fresh lane in one group with a resumed (skip) lane, fixed order:
+668 (seed 31) and 670 (seed 34). The 61 tests of the module take 19 s.
+"""
+import numpy as np
+import pytest
+
+from tests import progfuzz
+from wtf_amd.abi import EXIT_BREAKPOINT, EXIT_FAULT, RUNNING, regs_from_state
+
+pytestmark = pytest.mark.gpu
+
+N, N_PROGRAMS, LIMIT = 512, 16, 2000
+CASES = progfuzz.SHARED_CASES
+INT_A, INT_B, SSE, FP = CASES
+MORE = ((progfuzz.WIN2_VA, progfuzz.WIN2_LEN),)
+
+
+def case_id(c):
+    return f"seed{c[0]}" + ("-sse" if c[1] else "") + ("-fp" if c[2] else "")
+
+
+class Workload:
+    def __init__(self, case):
+        seed, sse, fp = case
+        self.case = case
+        self.sp, self.st, self.lanes, self.progs = progfuzz.build_shared_info(N, N_PROGRAMS, seed, sse=sse, fp=fp)
+        self.kw = {}
+        if sse:
+            self.kw = dict(xmm=progfuzz.lane_xmm(N, seed), ymmh=progfuzz.lane_xmm(N, seed, 0x4E4),
+                           mxcsr=progfuzz.lane_mxcsr(N, seed))
+        self.want = progfuzz.oracle_run(self.sp, self.st, self.lanes, limit=LIMIT, more=MORE, **self.kw)
+        self._bp = None
+
+    def breakpoints(self):
+        """The first instruction of about a quarter of every program's blocks,
+        one inside a counted loop and one jcc target among them where the
+        program has any."""
+        rng = np.random.RandomState(self.case[0])
+        bps = set()
+        for p in self.progs:
+            blocks = p["blocks"]
+            for sel in (lambda b: b[1], lambda b: b[2] and not b[1]):
+                some = [b[0] for b in blocks if sel(b)]
+                if some:
+                    bps.add(some[rng.randint(len(some))])
+            k = max(1, len(blocks) // 4)
+            bps.update(blocks[j][0] for j in rng.choice(len(blocks), k, replace=False))
+        return sorted(bps)
+
+    def want_bp(self):
+        """The oracle's run over the breakpoints: "stops" per lane, same final state."""
+        if self._bp is None:
+            self._bp = progfuzz.oracle_run(self.sp, self.st, self.lanes, limit=LIMIT, more=MORE,
+                                           breakpoints=self.breakpoints(), follow_bps=True, **self.kw)
+        return self._bp
+
+
+@pytest.fixture(scope="module")
+def workloads():
+    """case -> Workload; the oracle runs once per case, its results are shared
+    and never modified."""
+    cache = {}
+
+    def get(case):
+        if case not in cache:
+            cache[case] = Workload(case)
+        return cache[case]
+
+    return get
+
+
+# ---------------------------------------------------------------------------
+# engine side
+# ---------------------------------------------------------------------------
+def make_engine(w, breakpoints=(), code_pages=False):
+    """code_pages: the programs' pages get a coverage map (set_code_pages), so
+    that committed rips count as covered (UC_COVERED) instead of being logged."""
+    from wtf_amd.engine import Engine
+
+    eng = Engine(0)
+    pfns, blob = w.sp.phys()
+    eng.load_pool(pfns, blob)
+    eng.alloc_lanes(N, overlay_pages=16, cov_entries=4096)
+    eng.set_initial_state(regs_from_state(w.st))
+    eng.set_limit(LIMIT)
+    if breakpoints:
+        eng.set_breakpoints(list(breakpoints))
+    if code_pages:
+        eng.set_code_pages([(p["va"] >> 12) + k for p in w.progs for k in range(progfuzz.SLOT >> 12)])
+    load_lanes(eng, w)
+    return eng
+
+
+def load_lanes(eng, w):
+    eng.restore()
+    regs = eng.read_regs(0, N)
+    for i, (va, g, flags) in enumerate(w.lanes):
+        r = regs[i]
+        for k in range(16):
+            r.gpr[k] = g[k]
+        r.rip, r.rflags = va, flags
+        if w.kw:
+            for k in range(16):
+                r.xmm[k][0], r.xmm[k][1] = w.kw["xmm"][i][2 * k], w.kw["xmm"][i][2 * k + 1]
+                r.ymmh[k][0], r.ymmh[k][1] = w.kw["ymmh"][i][2 * k], w.kw["ymmh"][i][2 * k + 1]
+            r.mxcsr = w.kw["mxcsr"][i]
+    eng.write_regs(regs)
+
+
+class Totals:
+    def __init__(self):
+        self.calls = self.launches = self.group_steps = self.retired = 0
+
+    def add(self, st):
+        self.calls += 1
+        self.launches += st.kernel_launches
+        self.group_steps += st.group_steps
+        self.retired += st.lane_retired
+
+
+def running(eng):
+    return bool((eng.exits_np()["status"] == RUNNING).any())
+
+
+def run_sliced(eng, steps, tot=None, use_async=False):
+    """run(max_steps=steps) until no lane is RUNNING."""
+    tot = tot or Totals()
+    # a wave of 64 lanes at 2000 instructions each cannot take more wave-steps
+    for _ in range(64 * (LIMIT + 1) // steps + 2):
+        if use_async:
+            eng.run_async(0, N, steps)
+            tot.add(eng.run_wait())
+        else:
+            tot.add(eng.run(max_steps=steps))
+        if not running(eng):
+            return tot
+    raise AssertionError("lanes still running after every possible wave-step")
+
+
+def differences(eng, w, want, cov=True):
+    """Per-lane bit-exact comparison with the oracle's results."""
+    ex = eng.exits()
+    out = eng.read_regs(0, N)
+    covs, ovf = eng.coverage()
+    assert not ovf
+    nb = eng.nbytes()
+    bad = []
+    for i, x in enumerate(want):
+        e, r = ex[i], out[i]
+        f = e.status == EXIT_FAULT
+        got = (e.status, e.vector if f else 0, e.error if f else 0, e.addr if f else 0, r.rip, e.icount)
+        f = x["status"] == EXIT_FAULT
+        exp = (x["status"], x["vector"] if f else 0, x["error"] if f else 0, x["addr"] if f else 0, x["rip"], x["icount"])
+        prog = progfuzz.lane_program(i, N_PROGRAMS)
+        if got != exp:
+            bad.append((i, prog, "exit", got, exp))
+        elif [r.gpr[k] for k in range(16)] != x["gpr"] or r.rflags != x["rflags"]:
+            bad.append((i, prog, "regs", [hex(r.gpr[k]) for k in range(16)] + [hex(r.rflags)],
+                        [hex(v) for v in x["gpr"] + [x["rflags"]]]))
+        elif w.kw and ([r.xmm[k][h] for k in range(16) for h in range(2)] != x["xmm"] or r.mxcsr != x["mxcsr"]):
+            bad.append((i, prog, "xmm/mxcsr"))
+        elif w.kw and [r.ymmh[k][h] for k in range(16) for h in range(2)] != x["ymmh"]:
+            bad.append((i, prog, "ymmh"))
+        elif cov and covs.get(i, set()) != x["cov"]:
+            bad.append((i, prog, "cov", sorted(hex(v) for v in covs.get(i, set()) ^ x["cov"])[:8]))
+        elif set(eng.dirty(i)) != x["dirty"]:
+            bad.append((i, prog, "dirty", sorted(eng.dirty(i)), sorted(x["dirty"])))
+        elif int(nb[i]) != x["bytes"]:
+            bad.append((i, prog, "bytes", int(nb[i]), x["bytes"]))
+        elif i % 8 == 0 and (eng.read_virt(i, progfuzz.WIN_VA, 0x2000) != x["win"] or
+                             eng.read_virt(i, progfuzz.STACK_VA, 0x2000) != x["stack"] or
+                             eng.read_virt(i, MORE[0][0], MORE[0][1]) != x["more"][0]):
+            bad.append((i, prog, "memory"))
+    return bad
+
+
+def check(eng, w, want, shape, retired=None, cov=True):
+    bad = differences(eng, w, want, cov=cov)
+    assert not bad, (f"{case_id(w.case)} / {shape}: {len(bad)}/{N} lanes differ; "
+                     f"first (lane, program, what, got, expected): {bad[:3]}")
+    if retired is not None:
+        assert retired == sum(x["icount"] for x in want), shape
+
+
+# ---------------------------------------------------------------------------
+# 2. grouped execution, default settings
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_grouped_run_matches_oracle(case, workloads):
+    w = workloads(case)
+    eng = make_engine(w)
+    stats = eng.run()
+    check(eng, w, w.want, "default", retired=stats.lane_retired)
+    per_step = stats.lane_retired / stats.group_steps
+    print(f"{case_id(case)}: {per_step:.2f} lanes retired per wave-step, {stats.kernel_launches} launches")
+    # non-degeneracy: with a program per lane this cannot exceed 1.0
+    assert per_step > 2.0
+    eng.close()
+
+
+# ---------------------------------------------------------------------------
+# 3. the same workload under every launch shape
+# ---------------------------------------------------------------------------
+def accepts_run_at(eng, first):
+    """Whether a run may start at lane `first`: only at a multiple of the lanes
+    per wave. Asked when no lane is running: the launch retires nothing."""
+    from wtf_amd.engine import EngineError
+
+    try:
+        eng.run(first=first, count=first, max_steps=1)
+        return True
+    except EngineError:
+        return False
+
+
+def shape_fixed(w, mp):
+    mp.setenv("WTFGPU_REGROUP_STEPS", "0")
+    eng = make_engine(w)
+    st = eng.run()
+    assert st.kernel_launches == 1
+    assert not accepts_run_at(eng, 32) and not accepts_run_at(eng, 16)  # 64 lanes per wave
+    return eng, st.lane_retired
+
+
+def shape_regroup(w, mp):
+    mp.setenv("WTFGPU_REGROUP_AUTO", "0")
+    eng = make_engine(w)
+    eng.set_regroup(64)
+    st = eng.run()
+    assert st.kernel_launches >= 2
+    return eng, st.lane_retired
+
+
+def shape_sliced(steps):
+    def shape(w, mp):
+        eng = make_engine(w)
+        tot = run_sliced(eng, steps)
+        assert tot.calls > 1
+        return eng, tot.retired
+    return shape
+
+
+def shape_async(w, mp):
+    eng = make_engine(w)
+    tot = run_sliced(eng, 64, use_async=True)
+    assert tot.calls > 1
+    return eng, tot.retired
+
+
+def shape_lpw(lpw):
+    def shape(w, mp):
+        mp.setenv("WTFGPU_LPW", str(lpw))
+        eng = make_engine(w)
+        st = eng.run()
+        assert accepts_run_at(eng, lpw) and accepts_run_at(eng, 16) == (lpw == 16)
+        return eng, st.lane_retired
+    return shape
+
+
+def shape_cold_lds(w, mp):
+    mp.setenv("WTFGPU_WARM", "0")
+    eng = make_engine(w)
+    tot = run_sliced(eng, 64)
+    assert tot.calls > 1
+    return eng, tot.retired
+
+
+def shape_no_guc(w, mp):
+    mp.setenv("WTFGPU_GUC", "0")
+    eng = make_engine(w)
+    st = eng.run()
+    return eng, st.lane_retired
+
+
+def shape_code_pages(w, mp):
+    eng = make_engine(w, code_pages=True)  # nothing committed: every rip is still new to every lane
+    st = eng.run()
+    return eng, st.lane_retired
+
+
+def snapshot(eng):
+    return eng.exits_np().tobytes(), eng.read_gprs().tobytes(), eng.nbytes().tobytes()
+
+
+def shape_hot(w, mp):
+    eng = make_engine(w)
+    st = eng.run()
+    check(eng, w, w.want, "hot caches, first pass", retired=st.lane_retired)
+    first = snapshot(eng)
+    load_lanes(eng, w)
+    st = eng.run()
+    assert snapshot(eng) == first, "the second pass differs from the first"
+    return eng, st.lane_retired
+
+
+def shape_combined(w, mp):
+    mp.setenv("WTFGPU_REGROUP_AUTO", "0")
+    mp.setenv("WTFGPU_LPW", "16")
+    eng = make_engine(w)
+    eng.set_regroup(64)
+    tot = run_sliced(eng, 64)
+    assert tot.calls > 1 and accepts_run_at(eng, 16)
+    return eng, tot.retired
+
+
+SHAPES = {
+    "fixed-order": shape_fixed, "regroup-64": shape_regroup, "sliced-5": shape_sliced(5), "sliced-64": shape_sliced(64),
+    "async-64": shape_async, "lpw-32": shape_lpw(32), "lpw-16": shape_lpw(16), "cold-lds-sliced-64": shape_cold_lds,
+    "no-guc": shape_no_guc, "hot-caches": shape_hot, "code-pages": shape_code_pages,
+}
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_launch_shapes_match_oracle(case, shape, workloads, monkeypatch):
+    w = workloads(case)
+    eng, retired = SHAPES[shape](w, monkeypatch)
+    check(eng, w, w.want, shape, retired=retired)
+    eng.close()
+
+
+def test_regroup_sliced_lpw16_matches_oracle(workloads, monkeypatch):
+    w = workloads(FP)
+    eng, retired = shape_combined(w, monkeypatch)
+    check(eng, w, w.want, "regroup-64 + sliced-64 + lpw-16", retired=retired)
+    eng.close()
+
+
+# ---------------------------------------------------------------------------
+# 4. slice length does not depend on the path (U44)
+# ---------------------------------------------------------------------------
+def slice_records(eng):
+    """(status, rip, icount) of every lane after each 64 wave-step slice."""
+    recs = []
+    for _ in range(64 * (LIMIT + 1) // 64 + 2):
+        eng.run(max_steps=64)
+        ex = eng.exits_np()
+        recs.append(np.stack([ex["status"].astype(np.uint64), ex["rip"], ex["icount"]]))
+        if not (ex["status"] == RUNNING).any():
+            return recs
+    raise AssertionError("lanes still running after every possible wave-step")
+
+
+_BASELINE = {}
+
+
+def baseline_records(w):
+    """Variant (a): default caches. Fixed lane order, 64 lanes per wave."""
+    if w.case not in _BASELINE:
+        eng = make_engine(w)
+        _BASELINE[w.case] = slice_records(eng)
+        check(eng, w, w.want, "U44 baseline")
+        eng.close()
+    return _BASELINE[w.case]
+
+
+def assert_same_slices(got, base, what):
+    for k, (g, b) in enumerate(zip(got, base)):
+        if not np.array_equal(g, b):
+            lane = int(np.flatnonzero((g != b).any(axis=0))[0])
+            raise AssertionError(f"{what}: slice {k}, lane {lane} (program {progfuzz.lane_program(lane, N_PROGRAMS)}): "
+                                 f"(status, rip, icount) {[hex(int(v)) for v in g[:, lane]]}, "
+                                 f"default {[hex(int(v)) for v in b[:, lane]]}")
+    assert len(got) == len(base), f"{what}: {len(got)} slices, default {len(base)}"
+
+
+@pytest.mark.parametrize("variant", ["cold-lds", "no-guc", "second-pass", "coverage-committed"])
+@pytest.mark.parametrize("case", [INT_A, FP], ids=case_id)
+def test_slice_length_is_path_independent(case, variant, workloads, monkeypatch):
+    w = workloads(case)
+    monkeypatch.setenv("WTFGPU_REGROUP_STEPS", "0")
+    base = baseline_records(w)
+    cov = True
+    if variant == "cold-lds":
+        monkeypatch.setenv("WTFGPU_WARM", "0")
+    if variant == "no-guc":
+        monkeypatch.setenv("WTFGPU_GUC", "0")
+    eng = make_engine(w, code_pages=variant == "coverage-committed")
+    if variant == "second-pass":
+        assert_same_slices(slice_records(eng), base, "first pass")
+        load_lanes(eng, w)
+    if variant == "coverage-committed":
+        eng.commit_coverage(set().union(*(x["cov"] for x in w.want)))
+        load_lanes(eng, w)
+        cov = False  # committing empties the per-lane new-coverage sets by design
+    assert_same_slices(slice_records(eng), base, variant)
+    check(eng, w, w.want, f"U44 {variant}", cov=cov)
+    eng.close()
+
+
+# ---------------------------------------------------------------------------
+# 5. breakpoints, resume and mixed skip groups
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("regroup", [False, True], ids=["fixed-order", "regroup-64"])
+@pytest.mark.parametrize("case", [INT_A, FP], ids=case_id)
+def test_breakpoints_with_mixed_skip_groups(case, regroup, workloads, monkeypatch):
+    w = workloads(case)
+    want = w.want_bp()
+    assert sum(len(x["stops"]) for x in want) > N  # the breakpoints are hit
+    if regroup:
+        monkeypatch.setenv("WTFGPU_REGROUP_AUTO", "0")
+    else:
+        monkeypatch.setenv("WTFGPU_REGROUP_STEPS", "0")
+    eng = make_engine(w, breakpoints=w.breakpoints())
+    if regroup:
+        eng.set_regroup(64)
+    pos = [0] * N        # stops seen per lane
+    held = []            # stopped lanes left alone for one more round
+    tot = Totals()
+    mixed = 0            # a fresh lane met a resumed (skip) lane at its breakpoint: see below
+    before = eng.exits_np()
+    skip_at = set()      # (wave, rip) of the lanes resumed with skip before the last slice
+    bad = []
+    for _ in range(64 * (LIMIT + 1) // 64 + 2 * N):
+        tot.add(eng.run(max_steps=64))
+        ex = eng.exits_np()
+        stopped = [int(i) for i in np.flatnonzero(ex["status"] == EXIT_BREAKPOINT)]
+        if not stopped and not (ex["status"] == RUNNING).any():
+            break
+        new = [i for i in stopped if i not in held]
+        g = eng.read_gprs()
+        for i in new:
+            stops = want[i]["stops"]
+            got = (int(ex["rip"][i]), int(ex["icount"][i]), [int(v) for v in g[i, :16]])
+            if pos[i] >= len(stops) or got != stops[pos[i]]:
+                bad.append((i, progfuzz.lane_program(i, N_PROGRAMS), pos[i], got,
+                            stops[pos[i]] if pos[i] < len(stops) else None))
+            pos[i] += 1
+            # Fixed order, 64 lanes per wave: a group runs only when its rip is
+            # the lowest of the wave's running lanes. A lane that was behind a
+            # skip lane of its wave (lower rip, same program) when the slice
+            # began and now stops at that lane's breakpoint reached it while
+            # the skip lane still stood there: one group, skip set in a part.
+            if not regroup:
+                mixed += (i // 64, got[0]) in skip_at and int(before["rip"][i]) < got[0]
+        assert not bad, f"{case_id(case)}: (lane, program, stop number, got, expected): {bad[:3]}"
+        go = held + new[::2]   # every other new stop goes on now, the rest a round later
+        held = new[1::2]
+        eng.resume(go, [1] * len(go))
+        skip_at = {(i // 64, int(ex["rip"][i])) for i in go}
+        before = ex
+    else:
+        raise AssertionError("lanes still running or stopped after every possible round")
+    assert pos == [len(x["stops"]) for x in want]
+    check(eng, w, want, "breakpoints " + ("regroup-64" if regroup else "fixed-order"), retired=tot.retired)
+    if not regroup:
+        print(f"{case_id(case)}: {mixed} stops in a group with a skip lane")
+        assert mixed > 0
+    eng.close()

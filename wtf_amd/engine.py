@@ -100,6 +100,20 @@ class Engine:
         _chk(self.L.wtfgpu_run(self.ctx, first, count, max_steps, C.byref(st)), "run")
         return st
 
+    def set_regroup(self, steps):
+        """Wave-steps per launch between regrouping sorts (0: fixed lane order)."""
+        _chk(self.L.wtfgpu_set_regroup(self.ctx, steps), "set_regroup")
+
+    def run_async(self, first=0, count=None, max_steps=1 << 32):
+        """Queues a run of at most max_steps wave-steps; run_wait() collects it."""
+        count = self.nlanes - first if count is None else count
+        _chk(self.L.wtfgpu_run_async(self.ctx, first, count, max_steps), "run_async")
+
+    def run_wait(self) -> abi.RunStats:
+        st = abi.RunStats()
+        _chk(self.L.wtfgpu_run_wait(self.ctx, C.byref(st)), "run_wait")
+        return st
+
     def exits(self, first=0, count=None):
         count = self.nlanes - first if count is None else count
         arr = (abi.Exit * count)()
