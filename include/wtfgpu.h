@@ -31,6 +31,8 @@
  *   wtfgpu_read_coverage      <- AggregatedCodeCoverage_/LastNewCoverage_
  *                                (bochscpu_backend.cc:501-504, :1001-1016)
  *   wtfgpu_commit_coverage    <- AggregatedCodeCoverage_.emplace (bochscpu_backend.cc:501)
+ *   wtfgpu_attribute_coverage <- LastNewCoverage_ per testcase, in lane order, with
+ *                                RevokeLastNewCoverage (bochscpu_backend.cc:499-505, client.cc:120-126)
  *   wtfgpu_coverage_device_map, wtfgpu_coverage_absorb
  *                             <- the per-GPU coverage bitmap merged with RCCL MAX (new).
  */
@@ -433,6 +435,27 @@ int wtfgpu_read_coverage(wtfgpu_ctx *ctx, uint32_t first, uint32_t count, uint32
                          uint64_t *rips, uint64_t cap, uint64_t *n, uint32_t *overflow);
 /* Add RIPs to the coverage map (aggregate coverage). */
 int wtfgpu_commit_coverage(wtfgpu_ctx *ctx, const uint64_t *rips, uint64_t n);
+/* New coverage attributed in lane order on the device (LastNewCoverage,
+ * bochscpu_backend.cc:499-505, with the revocation of client.cc:120-126).
+ * lanes[0..n) are distinct lane ids (not checked) in attribution order, any
+ * order; revoke[i] != 0 marks a timed-out testcase (null: none). With A the
+ * device aggregate at the call (the coverage map, plus the set of values
+ * outside code pages), the result is what this walk emits:
+ *   for i in 0..n-1, for v in the sorted set of lanes[i]:
+ *     v in A: skip; else emit (i, v), and unless revoke[i], A += v (for this call)
+ * i.e. (i, v) with v not in A is emitted iff i <= the smallest non-revoked
+ * position that owns v. The entries come sorted by (i, v) in out_pos /
+ * out_vals; *total gets their number, *entries the raw live set entries
+ * examined, *overflow the OR of the listed lanes' overflow flags. With
+ * WTFGPU_ATTRIB_ALL nothing is filtered: each lane's whole sorted set. When
+ * cap >= *total the listed lanes' sets are emptied (as
+ * wtfgpu_collect_coverage_lanes does); otherwise nothing is, and the caller
+ * calls again with room. The aggregate itself is not modified: committing
+ * stays wtfgpu_commit_coverage. */
+#define WTFGPU_ATTRIB_ALL 1u
+int wtfgpu_attribute_coverage(wtfgpu_ctx *ctx, const uint32_t *lanes, const uint8_t *revoke, uint32_t n,
+                              uint32_t flags, uint32_t *out_pos, uint64_t *out_vals, uint64_t cap,
+                              uint64_t *total, uint64_t *entries, uint32_t *overflow);
 int wtfgpu_reset_coverage(wtfgpu_ctx *ctx);
 /* Edge coverage (--edges; RecordEdge, bochscpu_backend.cc:699-728): every
  * conditional near branch (taken or not) and indirect near jmp / call adds

@@ -62,6 +62,7 @@ class BpAction(C.Structure):
 
 
 BPACT_HOST, BPACT_RETURN, BPACT_SET_GPRS, BPACT_FEED = 0, 1, 2, 3
+ATTRIB_ALL = 1  # wtfgpu_attribute_coverage: no filter, each lane's whole sorted set
 
 
 class Write(C.Structure):
@@ -151,6 +152,9 @@ def load_hip_library(path: str = LIB_PATH) -> C.CDLL:
         "wtfgpu_read_coverage": ([P, U32, U32, C.POINTER(U32), C.POINTER(U64), U64, C.POINTER(U64),
                                   C.POINTER(U32)], C.c_int),
         "wtfgpu_commit_coverage": ([P, C.POINTER(U64), U64], C.c_int),
+        "wtfgpu_attribute_coverage": ([P, C.POINTER(U32), C.POINTER(C.c_uint8), U32, U32, C.POINTER(U32),
+                                       C.POINTER(U64), U64, C.POINTER(U64), C.POINTER(U64), C.POINTER(U32)],
+                                      C.c_int),
         "wtfgpu_reset_coverage": ([P], C.c_int),
         "wtfgpu_coverage_device_map": ([P, C.POINTER(P), C.POINTER(U64)], C.c_int),
         "wtfgpu_coverage_rips": ([P, C.POINTER(U64), U64, C.POINTER(U64)], C.c_int),

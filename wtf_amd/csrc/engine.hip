@@ -10,6 +10,7 @@
 // handlers, coverage log compaction and the aggregate coverage map.
 #include <hip/hip_runtime.h>
 #include <hipcub/device/device_radix_sort.hpp>
+#include <hipcub/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cstddef>
@@ -83,6 +84,8 @@ struct wtfgpu_ctx {
   u64 *d_rdseed = nullptr;    // per-lane Rdrand seeds (Dev::rd_seed)
   u64 *d_stopargs = nullptr;  // per-lane STOP_ARGS arguments (Dev::stop_args)
   u64 *d_extra = nullptr;     // coverage values outside code pages (Dev::extra_keys)
+  u8 *d_attr = nullptr;       // wtfgpu_attribute_coverage's candidates, owner table and result
+  u64 attr_bytes = 0;
   u8 *d_tn_buf = nullptr;     // Tenet traces (g_tn)
   u64 *d_tn_pos = nullptr, *d_tn_cpos = nullptr, *d_tn_ipos = nullptr, *d_tn_last = nullptr;
   u32 *d_tn_mute = nullptr;
@@ -505,6 +508,7 @@ int wtfgpu_destroy(wtfgpu_ctx *c) {
   for (QueueRes &q : c->queues)
     if (q.stream) (void)hipStreamSynchronize(q.stream);
   free_lanes(c);
+  dfree(c->d_attr);
   dfree(c->d_guc);
   if (c->d_warm) (void)hipFree(c->d_warm);
   dfree(c->d_pool);
@@ -1808,6 +1812,119 @@ int wtfgpu_collect_coverage_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t
   for (u32 i = 0; i < n; i++)
     if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
   return collect_sets(c, lanes, 0, n, out_lanes, out_rips, cap, total, overflow, 1);
+}
+
+// The new values of a lane list attributed in list order on the device (see
+// wtfgpu.h). Two device passes with one look at their counts between them:
+// most calls of a warmed-up campaign end at the first (no candidate left
+// after the filter against the aggregate).
+int wtfgpu_attribute_coverage(wtfgpu_ctx *c, const uint32_t *lanes, const uint8_t *revoke, uint32_t n, uint32_t flags,
+                              uint32_t *out_pos, uint64_t *out_vals, uint64_t cap, uint64_t *total, uint64_t *entries,
+                              uint32_t *overflow) {
+  if (!c || !total || (n && !lanes) || (cap && (!out_pos || !out_vals)) || (flags & ~(uint32_t)WTFGPU_ATTRIB_ALL))
+    return WTFGPU_ERR_INVALID;
+  *total = 0;
+  if (entries) *entries = 0;
+  if (overflow) *overflow = 0;
+  for (u32 i = 0; i < n; i++)
+    if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
+  if (!c->d_covrip || n == 0) return WTFGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const u32 all = flags & WTFGPU_ATTRIB_ALL ? 1 : 0;
+  const auto up = [](u64 v) { return (v + 255) & ~255ull; };
+  // queue scratch: lanes | revoke | cnt[n + 1] | off[n + 1] | header (entries, overflow) | scan scratch
+  size_t tmp_n = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_n, (u32 *)nullptr, (u32 *)nullptr, (int)(n + 1), c->stream));
+  const u64 o_rev = up((u64)n * 4), o_cnt = o_rev + up(n), o_off = o_cnt + up((u64)(n + 1) * 4),
+            o_hdr = o_off + up((u64)(n + 1) * 4), o_tmp = o_hdr + 256;
+  if (ensure_scratch(c, o_tmp + tmp_n)) return WTFGPU_ERR_OOM;
+  u8 *const S = c->d_scratch;
+  const u32 *d_lanes = (const u32 *)S;
+  const u8 *d_rev = S + o_rev;
+  u32 *d_cnt = (u32 *)(S + o_cnt), *d_off = (u32 *)(S + o_off);
+  HIPCHK(hipMemcpyAsync(S, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
+  if (revoke && !all)
+    HIPCHK(hipMemcpyAsync(S + o_rev, revoke, n, hipMemcpyHostToDevice, c->stream));
+  else
+    HIPCHK(hipMemsetAsync(S + o_rev, 0, n, c->stream));
+  HIPCHK(hipMemsetAsync(S + o_cnt, 0, (u64)(n + 1) * 4, c->stream));
+  HIPCHK(hipMemsetAsync(S + o_hdr, 0, 16, c->stream));
+  const u32 wblocks = (n + 3) / 4;
+  k_attr_scan<<<wblocks, 256, 0, c->stream>>>(c->P, d_lanes, n, all, d_cnt, nullptr, nullptr,
+                                              (unsigned long long *)(S + o_hdr), (u32 *)(S + o_hdr + 8));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(S + o_tmp, tmp_n, d_cnt, d_off, (int)(n + 1), c->stream));
+  u64 hdr[2] = {0, 0};
+  u32 s = 0;  // candidates (the scan's last sum; 32 bits hold nlanes * H of any context that fits the device)
+  HIPCHK(hipMemcpyAsync(hdr, S + o_hdr, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&s, d_off + n, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (entries) *entries = hdr[0];
+  if (overflow) *overflow = (u32)hdr[1] & 1;
+  const auto clear = [&]() -> int {  // everything was read: the sets empty (ordered before later work)
+    k_cov_clear<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, d_lanes, n);
+    HIPCHK(hipGetLastError());
+    return WTFGPU_OK;
+  };
+  if (s == 0) return clear();
+  if (all && cap < s) {  // parity mode emits every candidate: nothing more to learn without room
+    *total = s;
+    return WTFGPU_OK;
+  }
+  // own buffer: raw | vals | pos | slot | keys[T + 1] | own[T + 1] | flag[s + 1] | at[s + 1] | out_pos | out_vals | scan scratch
+  u32 T = 64;
+  while (T < 2ull * s && T < (1u << 31)) T <<= 1;
+  if (T < 2ull * s) return WTFGPU_ERR_OOM;
+  size_t tmp_s = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_s, (u32 *)nullptr, (u32 *)nullptr, (int)(s + 1), c->stream));
+  const u64 a_vals = up((u64)s * 8), a_pos = a_vals + up((u64)s * 8), a_slot = a_pos + up((u64)s * 4),
+            a_keys = a_slot + up((u64)s * 4), a_own = a_keys + up(((u64)T + 1) * 8),
+            a_flag = a_own + up(((u64)T + 1) * 4), a_at = a_flag + up(((u64)s + 1) * 4),
+            a_opos = a_at + up(((u64)s + 1) * 4), a_oval = a_opos + up((u64)s * 4), a_tmp = a_oval + up((u64)s * 8),
+            a_end = a_tmp + tmp_s;
+  if (c->attr_bytes < a_end) {
+    dfree(c->d_attr);
+    c->attr_bytes = 0;
+    const u64 want = std::max<u64>(a_end + a_end / 2, 1ull << 20);
+    if (hipMalloc((void **)&c->d_attr, want) != hipSuccess) return WTFGPU_ERR_OOM;
+    c->attr_bytes = want;
+  }
+  u8 *const A = c->d_attr;
+  u64 *d_raw = (u64 *)A, *d_vals = (u64 *)(A + a_vals);
+  u32 *d_pos = (u32 *)(A + a_pos);
+  k_attr_scan<<<wblocks, 256, 0, c->stream>>>(c->P, d_lanes, n, all, nullptr, d_off, d_raw, nullptr, nullptr);
+  HIPCHK(hipGetLastError());
+  k_attr_sort<<<wblocks, 256, 0, c->stream>>>(d_cnt, d_off, n, d_raw, d_vals, d_pos);
+  HIPCHK(hipGetLastError());
+  const u32 *d_rpos = d_pos;  // the result, on the device
+  const u64 *d_rvals = d_vals;
+  u32 m = s;
+  if (!all) {
+    u32 *d_slot = (u32 *)(A + a_slot), *d_own = (u32 *)(A + a_own), *d_flag = (u32 *)(A + a_flag),
+        *d_at = (u32 *)(A + a_at);
+    HIPCHK(hipMemsetAsync(A + a_keys, 0xff, a_flag - a_keys, c->stream));  // keys and own: all bits set
+    k_attr_owner<<<(s + 255) / 256, 256, 0, c->stream>>>(d_vals, d_pos, s, d_rev, (u64 *)(A + a_keys), d_own, T, d_slot);
+    HIPCHK(hipGetLastError());
+    k_attr_keep<<<s / 256 + 1, 256, 0, c->stream>>>(d_pos, d_slot, d_own, s, d_flag);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(A + a_tmp, tmp_s, d_flag, d_at, (int)(s + 1), c->stream));
+    k_attr_emit<<<(s + 255) / 256, 256, 0, c->stream>>>(d_vals, d_pos, d_flag, d_at, s, (u32 *)(A + a_opos),
+                                                        (u64 *)(A + a_oval));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&m, d_at + s, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    d_rpos = (const u32 *)(A + a_opos);
+    d_rvals = (const u64 *)(A + a_oval);
+  }
+  *total = m;
+  if (cap < m) return WTFGPU_OK;  // nothing emptied: the caller calls again with room
+  if (m) {
+    HIPCHK(hipMemcpyAsync(out_pos, d_rpos, (u64)m * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out_vals, d_rvals, (u64)m * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  const int rc = clear();
+  HIPCHK(hipStreamSynchronize(c->stream));  // d_attr serves both queues: idle at every return
+  return rc;
 }
 
 int wtfgpu_commit_coverage(wtfgpu_ctx *c, const uint64_t *rips, uint64_t n) {

@@ -561,4 +561,116 @@ __global__ void k_cov_commit(Dev P, const u64 *rips, u64 n) {
   }
 }
 
+// ---------------------------------------------------------------- coverage attribution
+// wtfgpu_attribute_coverage: the listed lanes' new values, attributed in list
+// order against the device aggregate. Position i of the list owns the values
+// of lane lanes[i]; every kernel here runs one wave per position or one thread
+// per candidate, and no result depends on which wave wins an atomic.
+
+// Is v in the device aggregate: its byte of cov_map when its page is a code
+// page, the extra set otherwise (where k_cov_commit put it).
+__device__ __forceinline__ bool cov_has(const Dev &P, u64 v) {
+  if (P.code_keys) {
+    u32 h = (u32)mix64(v >> 12) & P.code_mask;
+    for (u32 i = 0; i <= P.code_mask; i++) {
+      const u64 k = P.code_keys[h];
+      if (k == v >> 12) return P.cov_map[(u64)P.code_slot[h] * WTFGPU_PAGE_SIZE + (v & 0xfff)] != 0;
+      if (k == EMPTY_KEY) break;
+      h = (h + 1) & P.code_mask;
+    }
+  }
+  return P.extra_keys && v != EMPTY_KEY && set_has(P.extra_keys, P.extra_mask, v);
+}
+
+// Pass 1 (out == nullptr): cnt[i] = the candidates of position i (live entries
+// absent from the aggregate; with `all`, every live entry), plus the raw live
+// entries and the overflow flags of the list. An empty set costs one load.
+// Pass 2 (out != nullptr): the same walk writes the candidates to
+// out[off[i] ...], in slot order (ballot prefix: one order whatever the timing).
+__global__ void k_attr_scan(Dev P, const u32 *lanes, u32 n, u32 all, u32 *cnt, const u32 *off, u64 *out,
+                            unsigned long long *entries, u32 *ovf) {
+  const u32 i = rfl32(blockIdx.x * 4 + (threadIdx.x >> 6)), lid = threadIdx.x & 63;
+  if (i >= n) return;
+  const u32 lane = rfl32(lanes[i]);
+  if (!out && lid == 0 && P.cov_overflow[lane]) atomicOr(ovf, 1u);
+  u32 live = 0, keep = 0;
+  if (P.cov_cnt[lane]) {
+    const u32 g = P.lane_gen[lane], H = P.H;
+    const u64 base = (u64)lane * H;
+    const u32 at = out ? off[i] : 0, end = out ? off[i + 1] : 0;  // (off has n + 1 entries)
+    for (u32 k0 = 0; k0 < H; k0 += 64) {
+      const u32 k = k0 + lid;
+      const bool lv = k < H && P.cov_gen[base + k] == g;
+      const u64 v = lv ? P.cov_rip[base + k] : 0;
+      const bool kp = lv && (all || !cov_has(P, v));
+      const u64 mk = __ballot(kp);
+      const u32 to = at + keep + __popcll(mk & ((1ull << lid) - 1));
+      if (out && kp && to < end) out[to] = v;
+      live += __popcll(__ballot(lv));
+      keep += __popcll(mk);
+    }
+  }
+  if (out || lid) return;
+  cnt[i] = keep;
+  if (live) atomicAdd(entries, (unsigned long long)live);
+}
+
+// Position i's candidates sorted: each one's rank among them is its place (a
+// set holds a value once; equal values would keep their slot order). The
+// candidates of a lane are a handful once a campaign has warmed up.
+__global__ void k_attr_sort(const u32 *cnt, const u32 *off, u32 n, const u64 *in, u64 *vals, u32 *pos) {
+  const u32 i = rfl32(blockIdx.x * 4 + (threadIdx.x >> 6)), lid = threadIdx.x & 63;
+  if (i >= n) return;
+  const u32 c = rfl32(cnt[i]);
+  const u64 o = rfl32(off[i]);
+  for (u32 e = lid; e < c; e += 64) {
+    const u64 v = in[o + e];
+    u32 r = 0;
+    for (u32 j = 0; j < c; j++) {
+      const u64 w = in[o + j];
+      r += (w < v || (w == v && j < e)) ? 1u : 0u;
+    }
+    vals[o + r] = v;
+    pos[o + r] = i;
+  }
+}
+
+// First owner: own[slot of v] = the smallest position among v's owners that
+// are not revoked (~0: none). keys / own are T + 1 entries, all bits set; the
+// last serves the one value that equals the empty key. T >= 2 * s.
+__global__ void k_attr_owner(const u64 *vals, const u32 *pos, u32 s, const u8 *revoke, u64 *keys, u32 *own, u32 T,
+                             u32 *slot_of) {
+  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= s) return;
+  const u64 v = vals[j];
+  u32 h = T;
+  if (v != EMPTY_KEY) {
+    h = (u32)mix64(v) & (T - 1);
+    for (u32 t = 0; t < T; t++) {
+      const unsigned long long prev = atomicCAS((unsigned long long *)&keys[h], EMPTY_KEY, v);
+      if (prev == EMPTY_KEY || prev == v) break;
+      h = (h + 1) & (T - 1);
+    }
+  }
+  slot_of[j] = h;
+  if (!revoke[pos[j]]) atomicMin(&own[h], pos[j]);
+}
+
+// Candidate j is emitted iff its position is at most its value's first owner.
+__global__ void k_attr_keep(const u32 *pos, const u32 *slot_of, const u32 *own, u32 s, u32 *flag) {
+  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j > s) return;
+  flag[j] = j < s && pos[j] <= own[slot_of[j]] ? 1u : 0u;  // flag[s] = 0: the scan's last sum is the total
+}
+
+// The emitted candidates keep their (position, value) order: at[] is the
+// exclusive scan of flag[].
+__global__ void k_attr_emit(const u64 *vals, const u32 *pos, const u32 *flag, const u32 *at, u32 s, u32 *out_pos,
+                            u64 *out_vals) {
+  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= s || !flag[j]) return;
+  out_pos[at[j]] = pos[j];
+  out_vals[at[j]] = vals[j];
+}
+
 }  // namespace

@@ -215,6 +215,34 @@ class Engine:
         _chk(self.L.wtfgpu_commit_coverage(self.ctx, arr.ctypes.data_as(C.POINTER(C.c_uint64)), len(arr)),
              "commit_coverage")
 
+    def attribute_coverage(self, lanes, revoke=None, full=False):
+        """New coverage of `lanes` attributed in the given order on the device
+        (wtfgpu_attribute_coverage): (pos u32[], vals u64[], entries, overflow),
+        sorted by (position in lanes, value). A first call with cap=0 sizes the
+        buffers; the call that has room empties the lanes' sets."""
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        n = len(la)
+        rv = None if revoke is None else np.ascontiguousarray(np.asarray(revoke) != 0, dtype=np.uint8)
+        assert rv is None or len(rv) == n
+        flags = abi.ATTRIB_ALL if full else 0
+        total, entries, ovf = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        lp = la.ctypes.data_as(C.POINTER(C.c_uint32))
+        rp = None if rv is None else rv.ctypes.data_as(C.POINTER(C.c_uint8))
+
+        def call(pos, vals, room):
+            _chk(self.L.wtfgpu_attribute_coverage(
+                self.ctx, lp, rp, n, flags, None if pos is None else pos.ctypes.data_as(C.POINTER(C.c_uint32)),
+                None if vals is None else vals.ctypes.data_as(C.POINTER(C.c_uint64)), room, C.byref(total),
+                C.byref(entries), C.byref(ovf)), "attribute_coverage")
+
+        call(None, None, 0)
+        room = total.value
+        pos = np.zeros(room, dtype=np.uint32)
+        vals = np.zeros(room, dtype=np.uint64)
+        if room:
+            call(pos, vals, room)
+        return pos[: total.value], vals[: total.value], entries.value, bool(ovf.value)
+
     def nbytes(self, first=0, count=None) -> np.ndarray:
         count = self.nlanes - first if count is None else count
         out = np.zeros(count, dtype=np.uint64)

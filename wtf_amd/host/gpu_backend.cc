@@ -89,6 +89,7 @@ bool GpuBackend_t::Initialize(const Options_t &Opts, const CpuState_t &CpuState)
   touched_.assign(nlanes_, 0);
   pf_.assign(nlanes_, PrepFeed{});
   arenas_.resize(HostPool::Get().Threads() + 1);
+  if (const char *e = getenv("WTFGPU_DEVICE_ATTRIB")) device_attrib_ = device_attrib_ || atoi(e) != 0;
   if (Opts.Limit) SetLimit(Opts.Limit);
   if (Opts.Edges && wtfgpu_set_edges(ctx_, 1) != WTFGPU_OK) return false;  // bochscpu_backend.cc:308-312
   if (!Restore(CpuState)) return false;
@@ -1162,6 +1163,21 @@ bool GpuBackend_t::service_hits(const std::vector<uint32_t> &hits, uint32_t firs
 // (bochscpu_backend.cc:501-504); timed-out lanes have theirs revoked
 // (client.cc:122-125); the new rips join the device coverage map.
 void GpuBackend_t::finish_coverage(uint32_t n, std::vector<LaneResult> *out, std::vector<uint32_t> *timedout) {
+  if (device_attrib_ && !map_ahead_) {  // the same walk on the device (see attribute_on_device)
+    std::vector<uint32_t> all(n);
+    for (uint32_t l = 0; l < n; l++) all[l] = l;
+    attr_rev_.assign(n, 0);
+    if (timedout)
+      for (uint32_t l : *timedout) attr_rev_[l] = 1;
+    uint64_t got = 0;
+    uint32_t of = 0;
+    if (attribute_on_device(all.data(), n, got, of)) {
+      last_new_coverage_.clear();
+      apply_attribution(all.data(), got, out, n == 1);
+      if (full_coverage_) wtfgpu_reset_coverage(ctx_);  // parity mode: every lane ran against an empty map
+      return;
+    }
+  }
   uint64_t total = 0;
   uint32_t ovf = 0, dl = 0;
   uint64_t dr = 0;
@@ -1355,12 +1371,98 @@ void GpuBackend_t::target_restore(const Target_t &Target, const std::vector<uint
   cur_ = 0;
 }
 
+// New coverage attributed on the device (--device-attrib): lanes[0, n) in
+// order, attr_rev_[i] set for a timed-out testcase; the (position, value)
+// entries land in attr_pos_ / attr_vals_ and the lanes' sets are emptied.
+// False when the call fails (nothing was emptied: the host path serves).
+//
+// The device filters against its own aggregate (the coverage map and the set
+// of values outside code pages), which must hold nothing aggregate_ lacks: a
+// value only the device knew would be dropped for every owner, unreported.
+// Every writer keeps that order. commit_fresh and AbsorbExtra insert into
+// aggregate_ before wtfgpu_commit_coverage. A merge from other shards (RCCL:
+// rccl_exchange.cc's MergeEnd hands the merged map to MergeCoverageMap) goes
+// wtfgpu_coverage_merge_in, then AbsorbCoverageMap, inside one host call on
+// the thread that also attributes, so no attribution sees the map between the
+// two; the all-reduce itself works on a frozen copy, never on the live map.
+// Should the absorb fail, map_ahead_ is set and attribution stays on the host
+// until an absorb succeeds. The other direction is harmless and expected (the
+// device's extra set drops values once it is 3/4 full): apply_attribution
+// checks every entry against aggregate_ again.
+bool GpuBackend_t::attribute_on_device(const uint32_t *lanes, uint32_t n, uint64_t &total, uint32_t &ovf) {
+  const auto t0 = Clock::now();
+  if (attr_pos_.size() < (1u << 16)) {
+    attr_pos_.resize(1u << 16);
+    attr_vals_.resize(1u << 16);
+  }
+  const uint32_t flags = full_coverage_ ? WTFGPU_ATTRIB_ALL : 0;
+  uint64_t entries = 0;
+  total = 0;
+  int rc = wtfgpu_attribute_coverage(ctx_, lanes, attr_rev_.data(), n, flags, attr_pos_.data(), attr_vals_.data(),
+                                     attr_pos_.size(), &total, &entries, &ovf);
+  if (rc == WTFGPU_OK && total > attr_pos_.size()) {  // nothing was emptied: again, with room
+    attr_pos_.resize(total);
+    attr_vals_.resize(total);
+    rc = wtfgpu_attribute_coverage(ctx_, lanes, attr_rev_.data(), n, flags, attr_pos_.data(), attr_vals_.data(),
+                                   attr_pos_.size(), &total, &entries, &ovf);
+  }
+  if (rc != WTFGPU_OK || total > attr_pos_.size()) return false;
+  stats_.covlog_ms += ms_since(t0);
+  stats_.cov_entries += entries;
+  if (ovf && !cov_ovf_warned_) {
+    cov_ovf_warned_ = true;
+    fprintf(stderr, "wtfgpu: a lane's new-coverage set filled up (rips lost); raise the set size\n");
+  }
+  return true;
+}
+
+// The device's entries against the host aggregate, which stays the truth: a
+// value it already has is dropped for all its owners; the others are reported,
+// and committed by the owner that did not time out (one per value, by the
+// device's first-owner rule).
+void GpuBackend_t::apply_attribution(const uint32_t *lanes, uint64_t total, std::vector<LaneResult> *res, bool one) {
+  std::vector<uint64_t> fresh;
+  for (uint64_t k = 0; k < total; k++) {
+    const uint32_t at = attr_pos_[k], l = lanes[at];
+    const uint64_t v = attr_vals_[k];
+    if (full_coverage_) {  // parity mode: the lane's whole set, nothing committed
+      if (res) (*res)[l].new_coverage.push_back(v);
+      if (one) last_new_coverage_.insert(Gva_t(v));
+      continue;
+    }
+    if (aggregate_.count(v)) continue;
+    if (res) (*res)[l].new_coverage.push_back(v);
+    if (attr_rev_[at]) continue;
+    aggregate_.insert(v);
+    fresh.push_back(v);
+    if (one) last_new_coverage_.insert(Gva_t(v));
+  }
+  commit_fresh(fresh);
+}
+
 // Streaming form of finish_coverage: the finished lanes' new rips, attributed
 // in the given order against the aggregate (bochscpu_backend.cc:501-504);
 // timed-out lanes' are revoked (client.cc:122-125); the fresh ones join the
 // device map. Their log bits are dropped (the lanes get new testcases next).
 void GpuBackend_t::collect_coverage(const std::vector<uint32_t> &lanes, std::vector<LaneResult> &res,
                                     const uint64_t *pf_hdr) {
+  if (device_attrib_ && !map_ahead_ && !pf_hdr) {
+    attr_rev_.resize(lanes.size());
+    for (size_t i = 0; i < lanes.size(); i++) attr_rev_[i] = std::holds_alternative<Timedout_t>(res[lanes[i]].result);
+    uint64_t got = 0;
+    uint32_t of = 0;
+    if (attribute_on_device(lanes.data(), (uint32_t)lanes.size(), got, of)) {
+      const auto ta = Clock::now();
+      last_new_coverage_.clear();
+      apply_attribution(lanes.data(), got, &res, false);
+      // the lanes that had entries, for harvest_part's look at its plain lanes (by lane, as the host path leaves it)
+      cov_sorted_.resize(got);
+      for (uint64_t k = 0; k < got; k++) cov_sorted_[k] = {lanes[attr_pos_[k]], attr_vals_[k]};
+      if (!std::is_sorted(lanes.begin(), lanes.end())) std::sort(cov_sorted_.begin(), cov_sorted_.end());
+      stats_.attrib_ms += ms_since(ta);
+      return;
+    }
+  }
   const auto t0 = Clock::now();
   uint64_t total = 0;
   uint32_t ovf = 0;
@@ -1742,7 +1844,7 @@ bool GpuBackend_t::prefetch_part(Part &P) {
     return false;
   if (wtfgpu_prefetch_results(ctx_, P.lo, count, P.ex, P.nb, P.dc, args ? P.sargs : nullptr) != WTFGPU_OK)
     return false;
-  P.pf_cov = !full_coverage_ && wtfgpu_prefetch_coverage(ctx_, P.lo, count, P.cov_hdr) == WTFGPU_OK;
+  P.pf_cov = !full_coverage_ && !device_attrib_ && wtfgpu_prefetch_coverage(ctx_, P.lo, count, P.cov_hdr) == WTFGPU_OK;
   return true;
 }
 
@@ -2021,9 +2123,10 @@ std::string GpuBackend_t::StatsJson() const {
   r.pop_back();
   snprintf(b, sizeof(b), ",\"up_prep_ms\":%.3f,\"up_regs_ms\":%.3f,\"up_apply_ms\":%.3f,\"up_feed_ms\":%.3f,"
            "\"restore_dev_ms\":%.3f,\"out_ms\":%.3f,\"fresh_ms\":%.3f,\"occ_ms\":%.3f,\"harvest_ms\":%.3f,"
-           "\"prepared\":%llu",
+           "\"prepared\":%llu,\"device_attrib\":%d",
            stats_.up_prep_ms, stats_.up_regs_ms, stats_.up_apply_ms, stats_.up_feed_ms, stats_.restore_dev_ms,
-           stats_.out_ms, stats_.fresh_ms, stats_.occ_ms, stats_.harvest_ms, (unsigned long long)stats_.prepared);
+           stats_.out_ms, stats_.fresh_ms, stats_.occ_ms, stats_.harvest_ms, (unsigned long long)stats_.prepared,
+           device_attrib_ ? 1 : 0);
   r += b;
   r += ",\"unimpl_ops\":" + stats_.unimpl_ops.json();
   r += ",\"unimpl_raw\":" + stats_.unimpl_ops.raw_json();
@@ -2063,9 +2166,15 @@ bool GpuBackend_t::CoverageMap(uint8_t **Map, uint64_t *Bytes, bool *Device) {
 // since its last look; its own commits are not reported) join the aggregate.
 size_t GpuBackend_t::AbsorbCoverageMap() {
   uint64_t n = 0;
-  if (wtfgpu_coverage_absorb(ctx_, nullptr, 0, &n) != WTFGPU_OK || n == 0) return 0;
+  map_ahead_ = true;  // until the map's news are in the aggregate (see attribute_on_device)
+  if (wtfgpu_coverage_absorb(ctx_, nullptr, 0, &n) != WTFGPU_OK) return 0;
+  if (n == 0) {
+    map_ahead_ = false;
+    return 0;
+  }
   std::vector<uint64_t> rips(n);
-  if (wtfgpu_coverage_absorb(ctx_, rips.data(), n, &n) != WTFGPU_OK) return 0;
+  if (wtfgpu_coverage_absorb(ctx_, rips.data(), n, &n) != WTFGPU_OK || n > rips.size()) return 0;
+  map_ahead_ = false;
   size_t added = 0;
   for (uint64_t i = 0; i < n && i < rips.size(); i++) added += aggregate_.insert(rips[i]).second;
   return added;

@@ -111,6 +111,10 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
                   std::vector<StreamResult_t> &Out, ModuleSlots *Slots, size_t *Taken) override;
   void ResetCoverage() override;
   void SetFullCoverage(bool On) override { full_coverage_ = On; }
+  // --device-attrib (also WTFGPU_DEVICE_ATTRIB=1 in the environment, read by
+  // Initialize): new coverage is attributed on the device
+  // (wtfgpu_attribute_coverage) instead of from the raw (lane, rip) log
+  void SetDeviceAttrib(bool On) override { device_attrib_ = device_attrib_ || On; }
   void SetWantRegisters(bool On) override { want_gprs_ = On; }
   uint64_t LastIcount() const override { return last_icount_; }
   bool LastError() const override { return last_error_; }
@@ -384,6 +388,15 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   static thread_local bool scouting_;
   void learn(uint64_t gpfn) const;
   bool full_coverage_ = false;
+  // device attribution (attribute_on_device): the switch, the result buffers,
+  // and "the device map holds bits the aggregate lacks" (a failed absorb after
+  // a merge): while that holds, the host path attributes
+  bool device_attrib_ = false, map_ahead_ = false;
+  std::vector<uint32_t> attr_pos_;
+  std::vector<uint64_t> attr_vals_;
+  std::vector<uint8_t> attr_rev_;
+  bool attribute_on_device(const uint32_t *lanes, uint32_t n, uint64_t &total, uint32_t &ovf);
+  void apply_attribution(const uint32_t *lanes, uint64_t total, std::vector<LaneResult> *res, bool one);
 };
 
 

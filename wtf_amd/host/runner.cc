@@ -256,6 +256,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     else if (a == "--device") O.device = atoi(next("--device"));
     else if (a == "--full-coverage") O.full_coverage = true;
     else if (a == "--edges") O.edges = true;
+    else if (a == "--device-attrib") O.device_attrib = true;
     else if (a == "--trace-path") O.trace_path = next("--trace-path");
     else if (a == "--trace-type") O.trace_type = next("--trace-type");
     else if (a == "--trace-cap") O.trace_cap = (uint32_t)strtoul(next("--trace-cap"), nullptr, 0);
@@ -295,7 +296,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     fprintf(stderr, "usage: [run|fuzz|master] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
                     "       [--lanes n] [--overlay-pages k] [--runs n] [--seconds s] [--seed s] [--full-coverage]\n"
                     "       [--serial-mutation] [--slice-steps s] [--regroup-steps r] [--rank r --world n [--exchange host:port | --nccl-id-file f]]\n"
-                    "       [--address tcp://ip:port|unix://path [--batched] [--nodes k]] [--edges]\n"
+                    "       [--address tcp://ip:port|unix://path [--batched] [--nodes k]] [--edges] [--device-attrib]\n"
                     "       [--trace-path dir [--trace-type rip|cov|tenet] [--trace-cap n] [--tenet-cap bytes]] [--module-so m.so] [--serial]\n");
     return false;
   }
@@ -315,7 +316,8 @@ bool LoadTarget(const RunnerOptions &O, Options_t &Opts, CpuState_t &State) {
   Opts.GpuDevice = O.device;
   Opts.GpuLanes = O.lanes;
   Opts.GpuOverlayPages = O.overlay_pages;
-  if (O.full_coverage) Opts.GpuCoverageSet = 8192;
+  // (the streaming replay reads whole sets as well: see RunnerMain)
+  if (O.full_coverage || (O.mode == "run" && O.stream_run)) Opts.GpuCoverageSet = 8192;
   Opts.Fuzz.Seed = (uint32_t)O.seed;
   if (!LoadCpuStateFromJSON(State, Opts.CpuStatePath)) {
     printf("Failed to load the CPU state from %s\n", Opts.CpuStatePath.string().c_str());
@@ -357,6 +359,7 @@ int RunnerMain(const RunnerOptions &O, Executor_t &Exec, const Options_t &Opts, 
   Slots.Capture(N);
   Slots.AttachInstances(Inst.get());
   Exec.SetFullCoverage(O.full_coverage);
+  Exec.SetDeviceAttrib(O.device_attrib);  // run and fuzz, whole batches and streaming: one backend serves them all
 
   if (O.mode == "run") {
     auto Inputs = list_inputs(O.input.empty() ? fs::path(O.target) / "inputs" : fs::path(O.input));
@@ -512,7 +515,17 @@ int RunnerMain(const RunnerOptions &O, Executor_t &Exec, const Options_t &Opts, 
         print(In, L);
       }
     }
-    if (O.stream_run && Exec.CanStream() && !Trace) {
+    // Streaming replay without --full-coverage: testcases finish in another
+    // order than they were given, and one that finished early has committed
+    // rips a longer, earlier one then no longer logs, so the executor cannot
+    // attribute in input order itself. It reports every testcase's whole set
+    // (parity mode) and the walk of the serial client runs here, in input
+    // order: a testcase reports what no earlier one committed, a timed-out
+    // one commits nothing (bochscpu_backend.cc:499-505, client.cc:120-126).
+    const bool StreamReplay = O.stream_run && Exec.CanStream() && !Trace;
+    std::unordered_set<uint64_t> ReplaySeen;
+    if (StreamReplay && !O.full_coverage) Exec.SetFullCoverage(true);
+    if (StreamReplay) {
       // streaming replay: lanes refilled as testcases finish, results printed
       // in input order (parity with the batched replay, tests/test_gpu_tlv.py)
       std::vector<std::vector<uint8_t>> Bufs(Inputs.size());
@@ -539,11 +552,23 @@ int RunnerMain(const RunnerOptions &O, Executor_t &Exec, const Options_t &Opts, 
         }
       }
       for (size_t i = 0; i < Inputs.size(); i++) {
+        if (!O.full_coverage) {
+          std::vector<uint64_t> &Cov = Res[i].new_coverage, New;
+          std::sort(Cov.begin(), Cov.end());
+          Cov.erase(std::unique(Cov.begin(), Cov.end()), Cov.end());
+          const bool Revoke = std::holds_alternative<Timedout_t>(Res[i].result);
+          for (uint64_t V : Cov) {
+            if (ReplaySeen.count(V)) continue;
+            New.push_back(V);
+            if (!Revoke) ReplaySeen.insert(V);
+          }
+          Cov.swap(New);
+        }
         Retired += Res[i].icount;
         print(Inputs[i], Res[i]);
       }
     }
-    for (size_t b = (O.stream_run && Exec.CanStream() && !Trace) || (O.serial && !Trace) ? Inputs.size() : 0;
+    for (size_t b = StreamReplay || (O.serial && !Trace) ? Inputs.size() : 0;
          b < Inputs.size(); b += N) {
       const size_t n = std::min<size_t>(N, Inputs.size() - b);
       std::vector<std::vector<uint8_t>> Bufs(n);
@@ -568,7 +593,7 @@ int RunnerMain(const RunnerOptions &O, Executor_t &Exec, const Options_t &Opts, 
       }
     }
     if (Out != stdout) fclose(Out);
-    if (Stats) PrintTestcaseRunStats(Last, Exec.CoverageSize());
+    if (Stats) PrintTestcaseRunStats(Last, StreamReplay && !O.full_coverage ? ReplaySeen.size() : Exec.CoverageSize());
     if (!O.quiet)
       fprintf(stderr, "run: %zu testcases, %llu instructions, %.3f s\n", Inputs.size(), (unsigned long long)Retired,
               secs_since(t0));

@@ -95,6 +95,9 @@ class Executor_t {
   // parity mode: LaneResult::new_coverage holds each testcase's full rip set
   // (as if it ran first), not the lane-order delta
   virtual void SetFullCoverage(bool On) = 0;
+  // --device-attrib: an executor with a device attributes new coverage there
+  // (GpuBackend_t); the others have nothing to switch and compute the same
+  virtual void SetDeviceAttrib(bool) {}
   // LaneResult::gprs filled (run mode prints them; the fuzz loop does not read them)
   virtual void SetWantRegisters(bool) {}
   // the retired count / engine-error flag of the last Backend_t::Run
@@ -204,6 +207,7 @@ struct RunnerOptions {
   int device = 0;
   bool full_coverage = false;
   bool edges = false;        // --edges: branch edges join the coverage (RecordEdge)
+  bool device_attrib = false;  // --device-attrib: new coverage attributed in lane order on the GPU
   std::string trace_path;    // run: --trace-path dir (one <input>.trace per input, subcommands.cc:52-74)
   std::string trace_type = "rip";  // run: --trace-type rip | cov | tenet (wtf.cc:197-200)
   uint32_t trace_cap = 1u << 20;   // run: rips kept per testcase
