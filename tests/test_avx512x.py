@@ -1,0 +1,346 @@
+"""The AVX-512 integer forms of convention U49 (engine_avx512x.h): element-wise
+arithmetic, shifts and rotates, in-lane shuffles, cross-lane permutes, the
+widening loads, the 128- / 256-bit block moves, mask <-> vector and vmovd / q.
+
+Native-execution vectors (tests/golden/gen_avx512x_vectors.py) pin the
+engine's device code built for the host, generic and through the fast-loop
+digest. The oracle does not execute these forms yet, so there
+is no oracle comparison here. The GPU runs the same vectors in
+tests/test_gpu_avx512x.py.
+"""
+import ctypes as C
+import gzip
+import json
+import os
+
+import pytest
+
+from tests.golden.gen_avx512_vectors import case_inputs, guard_window
+from tests.golden.gen_avx512x_programs import GPR_INDEX, source
+from tests.golden.gen_avx512x_vectors import forms, lengths
+from tests.test_avx512 import WIN, XCR0, address_space, case_regs, check, get_zmm, sim_full
+from tests.test_sse import CODE_VA, SimResult
+from wtf_amd.abi import EXIT_FAULT, EXIT_INT3, EXIT_UNIMPLEMENTED, Regs, regs_from_state
+from wtf_amd.tools.snapshot import AddressSpace, user_state
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def load():
+    with gzip.open(os.path.join(HERE, "golden", "avx512x_vectors.json.gz"), "rt") as f:
+        return json.load(f)
+
+
+DOC = load()
+FAMILY = {f["nm"]: f["fam"] for f in forms()}
+with gzip.open(os.path.join(HERE, "golden", "avx512x_programs.json.gz"), "rt") as _f:
+    PROGS = json.load(_f)   # tests/golden/gen_avx512x_programs.py
+
+
+def inputs(c):
+    """(zmm0-31 as 256 u64, the window): case_inputs(seed), then the case's
+    deliberate inputs (zov: whole registers, wov: window bytes), then the guard."""
+    zmm, win = case_inputs(int(c["seed"], 16))
+    zmm = [list(v) for v in zmm]
+    for r, q in c.get("zov", []):
+        zmm[r] = [int(v, 16) for v in q]
+    win = bytearray(win)
+    for off, hx in c.get("wov", []):
+        bs = bytes.fromhex(hx)
+        win[off: off + len(bs)] = bs
+    return [v for r in zmm for v in r], guard_window(bytes(win), c["guard"])
+
+
+def sim_case(L, c, fast=False):
+    buf_va = int(DOC["buf_va"], 16)
+    zin, win = inputs(c)
+    sp = address_space(bytes.fromhex(c["code"]) + b"\xcc", buf_va, win, c["guard"])
+    regs = case_regs(c, regs_from_state(user_state(CODE_VA, 0, sp.cr3)), zin)
+    pfns, blob = sp.phys()
+    arr = (C.c_uint64 * len(pfns))(*pfns)
+    out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
+    L.sim_run_full(arr, blob, len(pfns), C.byref(regs), 0, C.byref(out), 1 if fast else 0, C.byref(cnt), buf_va,
+                   C.byref(fin), None)
+    if out.icount != (0 if "fault" in c else 1):
+        return ("icount", out.icount, out.status, out.vector)
+    return check(c, out.status, out.vector, out.error, out.addr, list(out.gpr), out.rflags, get_zmm(fin),
+                 list(fin.k), bytes(out.win[:WIN]), zin, win)
+
+
+@pytest.mark.parametrize("fast", [False, True], ids=["exec", "fast"])
+def test_engine_avx512x_code_matches_native_vectors(fast):
+    """The engine's decode / exec built for the host (tests/native/sim_lane.cc);
+    fast=True goes through k_run's fast-loop digest first (EVEX stays generic)."""
+    L = sim_full()
+    fails = []
+    for c in DOC["cases"]:
+        bad = sim_case(L, c, fast)
+        if bad:
+            fails.append((c["name"], c["code"]) + bad)
+    assert not fails, f"{len(fails)}/{len(DOC['cases'])} mismatches, first: {fails[:5]}"
+
+
+# Every mnemonic of the families that shipped, named here and
+# not taken from the generator: the names in the file come from the
+# disassembly of each case's own bytes.
+MNEMONICS = {
+    "A": "vpminsb vpminsw vpminsd vpminsq vpmaxsb vpmaxsw vpmaxsd vpmaxsq vpminud vpminuq vpmaxud vpmaxuq "
+         "vpabsb vpabsw vpabsd vpabsq vpaddsb vpaddsw vpaddusb vpaddusw vpsubsb vpsubsw vpsubusb vpsubusw "
+         "vpavgb vpavgw vpmullw vpmulhw vpmulhuw vpmulld vpmullq vpmuludq vpmuldq",
+    "B": "vpsrlw vpsrld vpsrlq vpsraw vpsrad vpsraq vpsllw vpslld vpsllq vprold vprolq vprord vprorq "
+         "vpsllvw vpsllvd vpsllvq vpsrlvw vpsrlvd vpsrlvq vpsravw vpsravd vpsravq vprolvd vprolvq vprorvd vprorvq "
+         "vpslldq vpsrldq",
+    "C": "vpshufb vpshufd vpshufhw vpshuflw vpunpcklbw vpunpcklwd vpunpckldq vpunpcklqdq vpunpckhbw vpunpckhwd "
+         "vpunpckhdq vpunpckhqdq vpacksswb vpackuswb vpackssdw vpackusdw vpalignr",
+    "D": "vpermd vpermq vpermw vpermb vpermi2b vpermi2w vpermi2d vpermi2q vpermt2b vpermt2w vpermt2d vpermt2q "
+         "valignd valignq vshufi32x4 vshufi64x2",
+    "E": "vpmovzxbw vpmovzxbd vpmovzxbq vpmovzxwd vpmovzxwq vpmovzxdq vpmovsxbw vpmovsxbd vpmovsxbq vpmovsxwd "
+         "vpmovsxwq vpmovsxdq",
+    "F": "vinserti32x4 vinserti64x2 vinserti32x8 vinserti64x4 vextracti32x4 vextracti64x2 vextracti32x8 "
+         "vextracti64x4 vbroadcasti32x2 vbroadcasti32x4 vbroadcasti64x2 vbroadcasti32x8 vbroadcasti64x4",
+    "G": "vpmovm2b vpmovm2w vpmovm2d vpmovm2q vpmovb2m vpmovw2m vpmovd2m vpmovq2m",
+    "H": "vmovd vmovq",
+}
+
+
+def fields(c):
+    """The EVEX fields of a case's code: (map, pp, W, L'L, z, b, aaa, reg, vvvv, opcode, mod, r/m register, imm8)."""
+    x = bytes.fromhex(c["code"])
+    assert x[0] == 0x62
+    p0, p1, p2, opc, modrm = x[1:6]
+    reg = ((modrm >> 3) & 7) | (((~p0 >> 7) & 1) << 3) | (((~p0 >> 4) & 1) << 4)
+    rm = (modrm & 7) | (((~p0 >> 5) & 1) << 3) | (((~p0 >> 6) & 1) << 4)
+    vvvv = ((~p1 >> 3) & 15) | (((~p2 >> 3) & 1) << 4)
+    return {"map": p0 & 7, "pp": p1 & 3, "w": p1 >> 7, "ll": (p2 >> 5) & 3, "z": p2 >> 7, "b": (p2 >> 4) & 1,
+            "aaa": p2 & 7, "reg": reg, "vvvv": vvvv, "opc": opc, "mod": modrm >> 6, "rm": rm, "imm": x[-1]}
+
+
+def rm_operand(c, e, nbytes):
+    """The first nbytes of a case's r/m operand: the register's, or the memory
+    operand's as the generator placed them (wov; an embedded broadcast repeated)."""
+    if e["mod"] == 3:
+        zin, _ = inputs(c)
+        return b"".join(v.to_bytes(8, "little") for v in zin[8 * e["rm"]: 8 * e["rm"] + 8])[:nbytes]
+    bs = bytes.fromhex(c["wov"][-1][1])
+    return (bs * (nbytes // len(bs)) if e["b"] else bs)[:nbytes]
+
+
+def test_avx512x_vector_file_is_substantial():
+    cases = DOC["cases"]
+    assert 2500 < len(cases) <= 6000
+    ok = [c for c in cases if not c["name"].startswith("ud.")]
+    # the mnemonics objdump gave the cases are exactly the shipped ones, and the generator's table names the same
+    for fam, names in MNEMONICS.items():
+        assert {c["name"].split(".")[0] for c in ok if FAMILY.get(c["name"].split(".")[0]) == fam} == set(names.split())
+    assert {c["name"].split(".")[0] for c in ok} == {n for v in MNEMONICS.values() for n in v.split()} == set(FAMILY)
+    # every mnemonic of the families that shipped, at every length it has, at least 8 cases each,
+    # from registers and from memory
+    per = {}
+    for c in ok:
+        if c["name"].endswith(".guard"):
+            continue
+        nm, ll, rm = c["name"].split(".")[:3]
+        per.setdefault((nm, ll), []).append(rm)
+    for f in forms():
+        for ll in lengths(f):
+            got = per.get((f["nm"], f"L{ll}"), [])
+            assert len(got) >= 8, (f["nm"], ll, got)
+            assert f.get("memonly") or "r" in got, (f["nm"], ll, got)
+            assert f.get("regonly") or "m" in got, (f["nm"], ll, got)
+    assert {FAMILY[c["name"].split(".")[0]] for c in ok} == set("ABCDEFGH")
+    # masks: about three quarters masked, a good part of those zeroing
+    masked = [c for c in ok if int(c["code"][6:8], 16) & 7]
+    maskable = [c for c in ok if FAMILY[c["name"].split(".")[0]] not in "GH" and "dq." not in c["name"]]
+    assert 0.6 < len(masked) / len(maskable) < 0.9
+    assert 0.25 < sum(int(c["code"][6:8], 16) >> 7 for c in masked) / len(masked) < 0.55
+    # broadcasts were met
+    assert sum((int(c["code"][6:8], 16) >> 4) & 1 for c in ok if "fault" not in c) > 150
+    for fam in "ABCDEFGH":
+        # memory fault suppression both ways: guard cases that fault and guard cases that complete
+        # (G has no memory forms)
+        guard = [c for c in ok if c["guard"] and FAMILY[c["name"].split(".")[0]] == fam]
+        assert fam == "G" or sum("fault" in c for c in guard) >= 8, fam
+        if fam in "AEF":  # the shuffles and permutes read their whole operand: every guard case of C / D faults
+            assert sum("fault" not in c for c in guard) >= 10, fam
+        # the #UD rules were met natively
+        ud = [c for c in cases if c["name"].startswith(f"ud.{fam}.")]
+        assert len(ud) >= 8 and all(c.get("fault", {}).get("vec") == 6 for c in ud), fam
+    rules = {c["name"].split(".")[2] for c in cases if c["name"].startswith("ud.")}
+    assert rules >= {"b_reg", "b_nobcast", "z_nomask", "vvvv_two", "vprime_two", "mask_bshift", "len128", "ll3",
+                     "w_fixed", "digit", "len_not512", "len_not128", "reg_memonly", "mem_regonly", "z_store",
+                     "mask_nomask"}
+    # deliberate inputs travel with the cases
+    assert sum("zov" in c or "wov" in c for c in ok) > 500
+
+
+# One representative of everything that stays outside: each is
+# a defined EVEX encoding, so it ends the testcase as UNIMPLEMENTED, not #UD.
+STILL_OUTSIDE = {
+    "vaddps zmm": "62f17c4858c1",
+    "vpmovwb ymm, zmm": "62f27e4830c1",
+    "vpmovdb xmm, zmm": "62f27e4831c1",
+    "vpcompressd zmm{k1}, zmm": "62f27d498bc1",
+    "vpexpandd zmm{k1}, zmm": "62f27d4989c1",
+    "vpgatherdd zmm{k1}, [rax+zmm1*4]": "62f27d49900488",
+    "vpscatterdd [rax+zmm1*4]{k1}, zmm0": "62f27d49a00488",
+    "vpconflictd zmm": "62f27d48c4c1",
+    "vplzcntd zmm": "62f27d4844c1",
+    "vpmaddwd zmm": "62f17548f5c2",
+    "vpsadbw zmm": "62f17548f6c2",
+    "vpmaddubsw zmm": "62f2754804c2",
+    "vpextrd eax, xmm1, 1": "62f37d0816c801",
+    "vpinsrd xmm0, xmm1, eax, 1": "62f3750822c001",
+    "vpmadd52luq zmm": "62f2f548b4c2",
+    "vpdpbusd zmm": "62f2754850c2",
+    "vpopcntb zmm": "62f27d4854c1",
+    "vpopcntd zmm": "62f27d4855c1",
+    "vaddph zmm": "62f57c4858c1",
+}
+
+
+@pytest.mark.parametrize("name", sorted(STILL_OUTSIDE))
+def test_evex_forms_outside_the_subset_stay_unimplemented(name):
+    L = sim_full()
+    c = next(c for c in DOC["cases"] if c["guard"] == 0 and "fault" not in c)
+    buf_va = int(DOC["buf_va"], 16)
+    zin, win = inputs(c)
+    sp = address_space(bytes.fromhex(STILL_OUTSIDE[name]) + b"\xcc", buf_va, win, 0)
+    regs = case_regs(c, regs_from_state(user_state(CODE_VA, 0, sp.cr3)), zin)
+    regs.gpr[0] = buf_va
+    regs.k[1] = 1
+    pfns, blob = sp.phys()
+    arr = (C.c_uint64 * len(pfns))(*pfns)
+    for fast in (0, 1):
+        out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
+        L.sim_run_full(arr, blob, len(pfns), C.byref(regs), 0, C.byref(out), fast, C.byref(cnt), buf_va,
+                       C.byref(fin), None)
+        assert out.status == EXIT_UNIMPLEMENTED and out.status not in (EXIT_FAULT, EXIT_INT3), (name, out.status,
+                                                                                                  out.vector)
+
+
+# ---------------------------------------------------------------- the multi-instruction routines
+def program_space():
+    """The routines at CODE_VA; four pages at the native run's buffer address:
+    source (per case), constants, and the two destination areas."""
+    lay = PROGS["layout"]
+    buf_va = int(PROGS["buf_va"], 16)
+    sp = AddressSpace()
+    sp.map_range(CODE_VA, bytes.fromhex(PROGS["code"]), write=False)
+    for off in (lay["src"], lay["dst"], lay["dst2"]):
+        sp.map(buf_va + off, b"")
+    sp.map(buf_va + lay["consts"], bytes.fromhex(PROGS["consts"]))
+    return sp
+
+
+def program_case(c, regs):
+    """Set a lane's registers for case c (the arguments the native harness
+    passed; every other GPR a value no routine relies on); returns its source bytes."""
+    lay = PROGS["layout"]
+    buf_va = int(PROGS["buf_va"], 16)
+    for i in range(16):
+        if i != 4:
+            regs.gpr[i] = 0x1111111111111111 * i
+    regs.gpr[7], regs.gpr[6] = buf_va + lay["src"], buf_va + lay["dst"]
+    regs.gpr[2], regs.gpr[1] = c["len"], buf_va + lay["consts"]
+    regs.rip = CODE_VA + PROGS["routines"][c["routine"]]["entry"]
+    regs.xcr0 = XCR0
+    return source(c["routine"], c["seed"])
+
+
+def program_check(c, icount, gpr, dst, dst2):
+    if icount != c["icount"]:
+        return ("icount", icount, c["icount"])
+    want = {nm: int(v, 16) for nm, v in zip(PROGS["gprs"], c["gpr"])}
+    got = {nm: gpr[GPR_INDEX[nm]] for nm in want}
+    if got != want:
+        return ("gpr", {nm: (hex(got[nm]), hex(want[nm])) for nm in want if got[nm] != want[nm]})
+    if dst != bytes.fromhex(c["dst"]):
+        return ("dst", [i for i in range(len(dst)) if dst[i] != bytes.fromhex(c["dst"])[i]][:8])
+    if dst2 != bytes.fromhex(c["dst2"]):
+        return ("dst2", [i for i in range(len(dst2)) if dst2[i] != bytes.fromhex(c["dst2"])[i]][:8])
+    return None
+
+
+@pytest.mark.parametrize("fast", [False, True], ids=["exec", "fast"])
+def test_engine_runs_avx512x_programs(fast):
+    """The natively recorded routines through the engine's host build, to their
+    int3: the retired count, the GPRs and both destination areas of every case."""
+    L = sim_full()
+    lay = PROGS["layout"]
+    buf_va = int(PROGS["buf_va"], 16)
+    assert {c["routine"] for c in PROGS["cases"]} == set(PROGS["routines"]) and len(PROGS["cases"]) == 32
+    fails = []
+    for c in PROGS["cases"]:
+        sp = program_space()
+        regs = regs_from_state(user_state(CODE_VA, 0, sp.cr3))
+        sp.write(buf_va + lay["src"], program_case(c, regs))
+        pfns, blob = sp.phys()
+        arr = (C.c_uint64 * len(pfns))(*pfns)
+        out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
+        ov = (C.c_uint8 * (64 * 4096))()
+        L.sim_run_full(arr, blob, len(pfns), C.byref(regs), 0, C.byref(out), 1 if fast else 0, C.byref(cnt), 0,
+                       C.byref(fin), ov)
+        if out.status != EXIT_INT3:
+            fails.append((c["routine"], c["len"], "exit", out.status, out.vector, hex(out.rip)))
+            continue
+        dirty = {out.dirty[k]: bytes(ov[4096 * k: 4096 * k + 4096]) for k in range(min(out.ovn, 64))}
+        area = [dirty.get(sp.translate(buf_va + lay[k]), bytes(4096))[:lay["area"]] for k in ("dst", "dst2")]
+        bad = program_check(c, out.icount, list(out.gpr), area[0], area[1])
+        if bad:
+            fails.append((c["routine"], c["len"]) + bad)
+        assert not fast or cnt.value > 0   # the VEX moves and the integer code took the fast loop's forms
+    assert not fails, f"{len(fails)}/{len(PROGS['cases'])}, first: {fails[:4]}"
+
+
+def test_vpabs_meets_its_minimum_in_a_selected_element():
+    """0x80..0 is vpabs's boundary operand (its own absolute value): every
+    vpabs form has it in an element its mask selects, at every length, from a
+    register and from memory."""
+    seen = set()
+    for c in DOC["cases"]:
+        nm = c["name"].split(".")[0]
+        if not nm.startswith("vpabs") or "fault" in c or c["guard"] or c["name"].startswith("ud."):
+            continue
+        e = fields(c)
+        es = {"b": 1, "w": 2, "d": 4, "q": 8}[nm[-1]]
+        n = (16 << e["ll"]) // es
+        sel = int(c["k"][e["aaa"]], 16) if e["aaa"] else ~0
+        src = rm_operand(c, e, n * es) if e["mod"] == 3 or "wov" in c else None
+        if src is None:
+            continue
+        minv = (1 << (8 * es - 1)).to_bytes(es, "little")
+        if any((sel >> j) & 1 and src[j * es: (j + 1) * es] == minv for j in range(n)):
+            seen.add((nm, e["ll"], "r" if e["mod"] == 3 else "m"))
+    assert seen == {(f"vpabs{s}", ll, rm) for s in "bwdq" for ll in range(3) for rm in "rm"}
+
+
+def test_shift_forms_meet_the_four_named_counts():
+    """Counts of 0, width - 1, width and beyond the width, in the imm8 forms,
+    the xmm / m128-count forms and the per-element forms, each from a register
+    and from memory."""
+    SH = ("vpsrl", "vpsra", "vpsll", "vprol", "vpror")
+    seen = {}
+    for c in DOC["cases"]:
+        nm = c["name"].split(".")[0]
+        if not nm.startswith(SH) or nm.endswith("dq") or "fault" in c or c["guard"] or c["name"].startswith("ud."):
+            continue
+        e = fields(c)
+        es = {"w": 2, "d": 4, "q": 8}[nm[-1]]
+        bits = 8 * es
+        if e["map"] == 1 and 0x71 <= e["opc"] <= 0x73:
+            kind, counts = "imm", [e["imm"]]
+        elif e["map"] == 1:
+            kind, counts = "xmm", [int.from_bytes(rm_operand(c, e, 8), "little")]
+        else:
+            kind = "var"
+            src = rm_operand(c, e, 16 << e["ll"])
+            counts = [int.from_bytes(src[j: j + es], "little") for j in range(0, len(src), es)]
+        got = seen.setdefault((nm, kind, "r" if e["mod"] == 3 else "m"), set())
+        for k in counts:
+            got.add("0" if k == 0 else "w-1" if k == bits - 1 else "w" if k == bits else ">w" if k > bits else "")
+    names = MNEMONICS["B"].split()
+    want = {(n, "var") for n in names if n[-2] == "v"} | {(n, "imm") for n in names if n[-2] != "v" and n[-2:] != "dq"} \
+        | {(n, "xmm") for n in names if n.startswith(SH[:3]) and n[-2] != "v" and n[-2:] != "dq"}
+    assert {k[:2] for k in seen} == want
+    for key, got in seen.items():
+        assert got >= {"0", "w-1", "w", ">w"}, (key, got)

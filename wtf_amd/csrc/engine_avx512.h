@@ -3,8 +3,21 @@
 // registers, vpternlog and broadcasts at 128 / 256 / 512 bits with merging or
 // zeroing masks, and the VEX-encoded opmask instructions (kmov, kortest,
 // ktest, kadd, kunpck, the k logic and shifts) — what vectorised memcpy / memset / strlen /
-// memchr / strcmp paths built for AVX-512 run. Every other EVEX encoding is
-// UNIMPLEMENTED (U36). The state (zmm0-31, k0-7) lives in the lane's cold
+// memchr / strcmp paths built for AVX-512 run — and the integer forms of U49
+// (engine_avx512x.h, evexx_exec): element-wise arithmetic (signed / unsigned
+// min / max, abs, saturating add / sub, avg, the multiplies), shifts and
+// rotates by imm8, by an xmm count and per element, vpslldq / vpsrldq, the
+// in-lane shuffles (vpshufb / d / hw / lw, vpunpck*, vpack*, vpalignr), the
+// cross-lane permutes (vpermb / w / d / q, vpermi2* / vpermt2*, valignd / q,
+// vshufi32x4 / 64x2), the widening loads vpmovzx* / vpmovsx*, and (evexm_exec)
+// the 128- / 256-bit block inserts / extracts / broadcasts, the mask <->
+// vector moves vpmovm2* / vpmov*2m and vmovd / vmovq. A form runs whether or
+// not CPUID leaf 7 names its extension (the DQ / VBMI variants differ from an
+// F / BW form only in W; a snapshot's guest chose its code paths on the
+// capture host). Every other EVEX encoding is UNIMPLEMENTED (U36): floating
+// point, the down-converts, compress / expand, gathers / scatters, vpconflict
+// / vplzcnt, vpmaddwd / vpsadbw / vpmaddubsw, vpextr / vpinsr, IFMA / VNNI /
+// BITALG / VPOPCNTDQ / FP16. The state (zmm0-31, k0-7) lives in the lane's cold
 // state (wtfgpu_regs_t: xmm / ymmh / zmmh for zmm0-15, zmm_hi for 16-31, k).
 //
 // Memory: an element whose mask bit is 0 is neither read nor written, so it
@@ -20,25 +33,76 @@ namespace wtfgpu_dev {
 
 // UOp::opreg of an EVEX op: O_SSE's VEX fields (bit 0 set, bit 2 W, bits 4-7
 // vvvv[3:0], bits 8-12 the map, bit 16 a prefix before it) plus bit 17 EVEX,
-// bits 18-19 L'L, bit 20 z, bit 21 b, bits 22-24 aaa, bit 25 V' (vvvv[4]).
+// bits 18-19 L'L, bit 21 z, bit 22 b, bits 23-25 aaa, bit 26 V' (vvvv[4]);
+// bit 27 carries R' through decode only; bit 28 marks a U49 form (evexx_exec),
+// with bit 29 its block / mask / GPR moves (evexm_exec).
+// Bit 20 is kMmxForm (engine_sse.h) and stays outside the EVEX fields.
 // UOp::reg and UOp::rm carry the 5-bit register numbers (R' and X included).
 constexpr u32 EVX = 1u << 17;
+constexpr u32 EVXX = 1u << 28;
+constexpr u32 EVXM = 1u << 29;
+static_assert(kMmxForm == (1u << 20) && !(kMmxForm & (EVX | EVXX | EVXM | (3u << 18) | (0x7fu << 21))),
+              "kMmxForm must stay outside the EVEX fields of UOp::opreg");
 __host__ __device__ inline u32 evex_ll(u32 x) { return (x >> 18) & 3; }
 __host__ __device__ inline u32 evex_vvvv(u32 x) { return ((x >> 4) & 15) | (((x >> 26) & 1) << 4); }
 
 enum : u32 {
   EZ_NONE = 0, EZ_MOV, EZ_LOGIC, EZ_ADD, EZ_SUB, EZ_MINU, EZ_MAXU, EZ_CMPEQ, EZ_CMPGT, EZ_CMP, EZ_TESTM,
-  EZ_TERN, EZ_BCAST, EZ_BCASTR
+  EZ_TERN, EZ_BCAST, EZ_BCASTR,
+  EZ_WUD = 15,  // #UD at decode (native execution): the opcode is in the subset, this W or /digit is not
+  // U49 (engine_avx512x.h): kinds from EZ_X on run in evexx_exec
+  EZ_X = 16, EZ_BIN = EZ_X, EZ_UN, EZ_SHI, EZ_SHX, EZ_BSH, EZ_PSHUFB, EZ_PSHUFD, EZ_PSHUFW, EZ_UNPCK, EZ_PACK,
+  EZ_ALIGNR, EZ_PERM, EZ_PERMQI, EZ_PERMI2, EZ_PERMT2, EZ_VALIGN, EZ_SHUFI, EZ_PMOVX,
+  // kinds from EZ_Y on run in evexm_exec: 128- / 256-bit block insert, extract and broadcast, mask <-> vector,
+  // vmovd / vmovq
+  EZ_Y = 40, EZ_INS = EZ_Y, EZ_EXT, EZ_BCB, EZ_M2V, EZ_V2M, EZ_GMOV
+};
+// EZ_BIN's sub
+enum : u32 {
+  XB_MINS = 0, XB_MAXS, XB_MINU, XB_MAXU, XB_ADDS, XB_ADDUS, XB_SUBS, XB_SUBUS, XB_AVG, XB_MULL, XB_MULH, XB_MULHU,
+  XB_MULUDQ, XB_MULDQ, XB_SLLV, XB_SRLV, XB_SRAV, XB_ROLV, XB_RORV
+};
+// the shifts' sub (EZ_SHI / EZ_SHX): XS_ROR / XS_ROL by imm8 only
+enum : u32 { XS_SRL = 0, XS_SRA, XS_SLL, XS_ROR, XS_ROL };
+// The memory operand's size class: what disp8 scales by (SDM 2.7.5) and how
+// many bytes the operand has. MC_FULL: the vector, or one element under
+// EVEX.b; MC_FULLMEM: the vector, no broadcast (the byte / word forms);
+// MC_HALF / QUARTER / EIGHTH: that part of the vector (vpmovzx / sx);
+// MC_M128: 16 bytes at every length (the shifts' xmm count); MC_T8 / T16 /
+// T32: the 8- / 16- / 32-byte tuples of the block forms; MC_T1S: one scalar
+// of the element size (vmovd / vmovq).
+enum : u32 { MC_FULL = 0, MC_FULLMEM, MC_HALF, MC_QUARTER, MC_EIGHTH, MC_M128, MC_T8, MC_T16, MC_T32, MC_T1S };
+enum : u32 {
+  XF_IMM = 1, XF_TWO = 2, XF_VDST = 4, XF_NOMASK = 8, XF_NF = 16, XF_NO128 = 32, XF_ONLY512 = 64, XF_ONLY128 = 128,
+  XF_MEMONLY = 256, XF_REGONLY = 512
 };
 struct EForm {
   u32 kind, es, sub;  // sub: logic op (0 and 1 andn 2 or 3 xor), cmp signedness (1 signed), testm negation
   bool store, aligned, bcastok, kdest;
   bool nt = false;    // the non-temporal moves: memory operand only, no masking (aaa != 0: #UD)
+  // U49
+  u32 mc = MC_FULL;
+  u32 ses = 0;        // the source's element (vpmovzx / sx, the packs): also what EVEX.b broadcasts; the block
+                      // forms' block bytes
+  u32 fl = 0;         // XF_IMM an imm8 follows; XF_TWO no vvvv operand; XF_VDST the destination is vvvv (ModRM.reg
+                      // a /digit); XF_NOMASK aaa != 0 is #UD; XF_NF a masked-off element of a memory source is
+                      // still read (no fault suppression); XF_NO128 no 128-bit form; XF_ONLY512 / XF_ONLY128
+                      // that length alone; XF_MEMONLY / XF_REGONLY no register / memory r/m operand
 };
+__host__ __device__ inline EForm xform(u32 kind, u32 es, u32 sub, bool bc, u32 fl = 0, u32 mc = MC_FULL, u32 ses = 0) {
+  EForm f{kind, es, sub, false, false, bc, false};
+  f.mc = (mc == MC_FULL && !bc) ? (u32)MC_FULLMEM : mc;
+  f.ses = ses ? ses : es;
+  f.fl = fl;
+  return f;
+}
 
 // The subset, by (map, opcode, pp, W). pp: 0 none, 1 66, 2 f3, 3 f2.
-__host__ __device__ inline EForm evex_form(u32 map, u32 c, u32 pp, u32 w) {
+// digit: ModRM.reg[2:0], which selects the form of the groups 0f 71 / 72 / 73.
+__host__ __device__ inline EForm evex_form(u32 map, u32 c, u32 pp, u32 w, u32 digit = 0) {
   EForm f{EZ_NONE, 0, 0, false, false, false, false};
+  const EForm wud{EZ_WUD, 0, 0, false, false, false, false};  // a U49 opcode at a W or /digit it does not have
+  const u32 wes = w ? 8u : 4u;
   if (map == 1) {
     if ((c == 0x10 || c == 0x11 || c == 0x28 || c == 0x29) && pp <= 1 && w == pp)  // vmovups/upd, vmovaps/apd
       return EForm{EZ_MOV, pp ? 8u : 4u, 0, (c & 1) != 0, c >= 0x28, false, false};
@@ -50,8 +114,66 @@ __host__ __device__ inline EForm evex_form(u32 map, u32 c, u32 pp, u32 w) {
       if (pp == 3) return EForm{EZ_MOV, w ? 2u : 1u, 0, c == 0x7f, false, false, false};  // vmovdqu8 / 16
       return f;
     }
+    if (c == 0x70) {  // vpshufd / vpshufhw / vpshuflw
+      if (pp == 1) return w ? wud : xform(EZ_PSHUFD, 4, 0, true, XF_IMM | XF_TWO | XF_NF);
+      if (pp == 2 || pp == 3) return xform(EZ_PSHUFW, 2, pp == 2 ? 1 : 0, false, XF_IMM | XF_TWO | XF_NF);
+      return f;
+    }
+    // vmovd / vmovq (128 bits, no mask): sub 0 xmm <- r/m32 / 64, 1 r/m32 / 64 <- xmm, 2 xmm <- xmm / m64, 3 xmm / m64 <- xmm
+    if (c == 0x6e && pp == 1) return xform(EZ_GMOV, wes, 0, false, XF_TWO | XF_NOMASK | XF_ONLY128, MC_T1S);
+    if (c == 0x7e && pp == 1) return xform(EZ_GMOV, wes, 1, false, XF_TWO | XF_NOMASK | XF_ONLY128, MC_T1S);
+    if (c == 0x7e && pp == 2) return w ? xform(EZ_GMOV, 8, 2, false, XF_TWO | XF_NOMASK | XF_ONLY128, MC_T1S) : wud;
+    if (c == 0xd6 && pp == 1) return w ? xform(EZ_GMOV, 8, 3, false, XF_TWO | XF_NOMASK | XF_ONLY128, MC_T1S) : wud;
     if (pp != 1) return f;
     switch (c) {
+      case 0x60: return xform(EZ_UNPCK, 1, 0, false, XF_NF);
+      case 0x61: return xform(EZ_UNPCK, 2, 0, false, XF_NF);
+      case 0x62: return w ? wud : xform(EZ_UNPCK, 4, 0, true, XF_NF);
+      case 0x6c: return w ? xform(EZ_UNPCK, 8, 0, true, XF_NF) : wud;
+      case 0x68: return xform(EZ_UNPCK, 1, 1, false, XF_NF);
+      case 0x69: return xform(EZ_UNPCK, 2, 1, false, XF_NF);
+      case 0x6a: return w ? wud : xform(EZ_UNPCK, 4, 1, true, XF_NF);
+      case 0x6d: return w ? xform(EZ_UNPCK, 8, 1, true, XF_NF) : wud;
+      case 0x63: return xform(EZ_PACK, 1, 0, false, XF_NF, MC_FULL, 2);  // vpacksswb
+      case 0x67: return xform(EZ_PACK, 1, 1, false, XF_NF, MC_FULL, 2);  // vpackuswb
+      case 0x6b: return w ? wud : xform(EZ_PACK, 2, 0, true, XF_NF, MC_FULL, 4);  // vpackssdw
+      case 0x71:  // vpsrlw / vpsraw / vpsllw by imm8
+        if (digit == 2 || digit == 4 || digit == 6)
+          return xform(EZ_SHI, 2, digit == 2 ? XS_SRL : digit == 4 ? XS_SRA : XS_SLL, false, XF_IMM | XF_VDST);
+        return wud;
+      case 0x72:  // vprord / q, vprold / q, vpsrld, vpsrad / q, vpslld
+        if (digit == 0 || digit == 1) return xform(EZ_SHI, wes, digit ? XS_ROL : XS_ROR, true, XF_IMM | XF_VDST);
+        if (digit == 4) return xform(EZ_SHI, wes, XS_SRA, true, XF_IMM | XF_VDST);
+        if ((digit == 2 || digit == 6) && !w) return xform(EZ_SHI, 4, digit == 2 ? XS_SRL : XS_SLL, true, XF_IMM | XF_VDST);
+        return wud;
+      case 0x73:  // vpsrlq, vpsrldq, vpsllq, vpslldq
+        if ((digit == 2 || digit == 6) && w) return xform(EZ_SHI, 8, digit == 2 ? XS_SRL : XS_SLL, true, XF_IMM | XF_VDST);
+        if (digit == 3 || digit == 7) return xform(EZ_BSH, 1, digit == 7, false, XF_IMM | XF_VDST | XF_NOMASK | XF_NF);
+        return wud;
+      case 0xd1: return xform(EZ_SHX, 2, XS_SRL, false, XF_NF, MC_M128);
+      case 0xd2: return w ? wud : xform(EZ_SHX, 4, XS_SRL, false, XF_NF, MC_M128);
+      case 0xd3: return w ? xform(EZ_SHX, 8, XS_SRL, false, XF_NF, MC_M128) : wud;
+      case 0xe1: return xform(EZ_SHX, 2, XS_SRA, false, XF_NF, MC_M128);
+      case 0xe2: return xform(EZ_SHX, wes, XS_SRA, false, XF_NF, MC_M128);
+      case 0xf1: return xform(EZ_SHX, 2, XS_SLL, false, XF_NF, MC_M128);
+      case 0xf2: return w ? wud : xform(EZ_SHX, 4, XS_SLL, false, XF_NF, MC_M128);
+      case 0xf3: return w ? xform(EZ_SHX, 8, XS_SLL, false, XF_NF, MC_M128) : wud;
+      case 0xd5: return xform(EZ_BIN, 2, XB_MULL, false);
+      case 0xe4: return xform(EZ_BIN, 2, XB_MULHU, false);
+      case 0xe5: return xform(EZ_BIN, 2, XB_MULH, false);
+      case 0xd8: return xform(EZ_BIN, 1, XB_SUBUS, false);
+      case 0xd9: return xform(EZ_BIN, 2, XB_SUBUS, false);
+      case 0xdc: return xform(EZ_BIN, 1, XB_ADDUS, false);
+      case 0xdd: return xform(EZ_BIN, 2, XB_ADDUS, false);
+      case 0xe8: return xform(EZ_BIN, 1, XB_SUBS, false);
+      case 0xe9: return xform(EZ_BIN, 2, XB_SUBS, false);
+      case 0xec: return xform(EZ_BIN, 1, XB_ADDS, false);
+      case 0xed: return xform(EZ_BIN, 2, XB_ADDS, false);
+      case 0xe0: return xform(EZ_BIN, 1, XB_AVG, false);
+      case 0xe3: return xform(EZ_BIN, 2, XB_AVG, false);
+      case 0xea: return xform(EZ_BIN, 2, XB_MINS, false);
+      case 0xee: return xform(EZ_BIN, 2, XB_MAXS, false);
+      case 0xf4: return w ? xform(EZ_BIN, 8, XB_MULUDQ, true) : wud;
       case 0xdb: return EForm{EZ_LOGIC, w ? 8u : 4u, 0, false, false, true, false};
       case 0xdf: return EForm{EZ_LOGIC, w ? 8u : 4u, 1, false, false, true, false};
       case 0xeb: return EForm{EZ_LOGIC, w ? 8u : 4u, 2, false, false, true, false};
@@ -79,8 +201,50 @@ __host__ __device__ inline EForm evex_form(u32 map, u32 c, u32 pp, u32 w) {
     if ((c == 0x26 || c == 0x27) && (pp == 1 || pp == 2))  // vptestm / vptestnm b w (26), d q (27)
       return EForm{EZ_TESTM, c == 0x26 ? (w ? 2u : 1u) : (w ? 8u : 4u), pp == 2 ? 1u : 0u, false, false, c == 0x27,
                    true};
+    if (pp == 2) {  // vpmovm2 b w d q, vpmov b w d q 2m (no mask, registers only)
+      if (c == 0x28 || c == 0x38) return xform(EZ_M2V, c == 0x28 ? (w ? 2u : 1u) : wes, 0, false, XF_TWO | XF_NOMASK | XF_REGONLY);
+      if (c == 0x29 || c == 0x39) return xform(EZ_V2M, c == 0x29 ? (w ? 2u : 1u) : wes, 0, false, XF_TWO | XF_NOMASK | XF_REGONLY);
+    }
     if (pp != 1) return f;
+    if (c == 0x59 && !w) return xform(EZ_BCB, 4, 0, false, XF_TWO, MC_T8, 8);                      // vbroadcasti32x2
+    if (c == 0x5a) return xform(EZ_BCB, wes, 0, false, XF_TWO | XF_NO128 | XF_MEMONLY, MC_T16, 16);    // 32x4 / 64x2
+    if (c == 0x5b) return xform(EZ_BCB, wes, 0, false, XF_TWO | XF_ONLY512 | XF_MEMONLY, MC_T32, 32);  // 32x8 / 64x4
+    if ((c >= 0x20 && c <= 0x25) || (c >= 0x30 && c <= 0x35)) {  // vpmovsx / vpmovzx bw bd bq wd wq dq
+      const u32 t = c & 15, sgn = c < 0x30;
+      if (t == 5 && w) return wud;
+      const u32 des = t == 0 ? 2u : (t == 1 || t == 3) ? 4u : 8u, ses = t < 3 ? 1u : t < 5 ? 2u : 4u;
+      return xform(EZ_PMOVX, des, sgn, false, XF_TWO, des / ses == 2 ? MC_HALF : des / ses == 4 ? MC_QUARTER : MC_EIGHTH,
+                   ses);
+    }
     switch (c) {
+      case 0x00: return xform(EZ_PSHUFB, 1, 0, false, XF_NF);
+      case 0x1c: return xform(EZ_UN, 1, 0, false, XF_TWO);
+      case 0x1d: return xform(EZ_UN, 2, 0, false, XF_TWO);
+      case 0x1e: return w ? wud : xform(EZ_UN, 4, 0, true, XF_TWO);
+      case 0x1f: return w ? xform(EZ_UN, 8, 0, true, XF_TWO) : wud;
+      case 0x28: return w ? xform(EZ_BIN, 8, XB_MULDQ, true) : wud;
+      case 0x2b: return w ? wud : xform(EZ_PACK, 2, 1, true, XF_NF, MC_FULL, 4);  // vpackusdw
+      case 0x38: return xform(EZ_BIN, 1, XB_MINS, false);
+      case 0x39: return xform(EZ_BIN, wes, XB_MINS, true);
+      case 0x3b: return xform(EZ_BIN, wes, XB_MINU, true);
+      case 0x3c: return xform(EZ_BIN, 1, XB_MAXS, false);
+      case 0x3d: return xform(EZ_BIN, wes, XB_MAXS, true);
+      case 0x3f: return xform(EZ_BIN, wes, XB_MAXU, true);
+      case 0x40: return xform(EZ_BIN, wes, XB_MULL, true);
+      case 0x10: return w ? xform(EZ_BIN, 2, XB_SRLV, false) : wud;
+      case 0x11: return w ? xform(EZ_BIN, 2, XB_SRAV, false) : wud;
+      case 0x12: return w ? xform(EZ_BIN, 2, XB_SLLV, false) : wud;
+      case 0x45: return xform(EZ_BIN, wes, XB_SRLV, true);
+      case 0x46: return xform(EZ_BIN, wes, XB_SRAV, true);
+      case 0x47: return xform(EZ_BIN, wes, XB_SLLV, true);
+      case 0x14: return xform(EZ_BIN, wes, XB_RORV, true);
+      case 0x15: return xform(EZ_BIN, wes, XB_ROLV, true);
+      case 0x36: return xform(EZ_PERM, wes, 0, true, XF_NF | XF_NO128);
+      case 0x8d: return xform(EZ_PERM, w ? 2 : 1, 0, false, XF_NF);
+      case 0x75: return xform(EZ_PERMI2, w ? 2 : 1, 0, false, XF_NF);
+      case 0x76: return xform(EZ_PERMI2, wes, 0, true, XF_NF);
+      case 0x7d: return xform(EZ_PERMT2, w ? 2 : 1, 0, false, XF_NF);
+      case 0x7e: return xform(EZ_PERMT2, wes, 0, true, XF_NF);
       case 0x2a: return w ? f : EForm{EZ_MOV, 4, 0, false, true, false, false, true};  // vmovntdqa
       case 0x29: return w ? EForm{EZ_CMPEQ, 8, 0, false, false, true, true} : f;
       case 0x37: return w ? EForm{EZ_CMPGT, 8, 0, false, false, true, true} : f;
@@ -97,6 +261,15 @@ __host__ __device__ inline EForm evex_form(u32 map, u32 c, u32 pp, u32 w) {
     }
   }
   if (map == 3 && pp == 1) {
+    // vinserti / vextracti 32x4, 64x2 (16-byte blocks; 256 and 512 bits) and 32x8, 64x4 (32-byte blocks; 512 bits)
+    if (c == 0x38) return xform(EZ_INS, wes, 0, false, XF_IMM | XF_NF | XF_NO128, MC_T16, 16);
+    if (c == 0x3a) return xform(EZ_INS, wes, 0, false, XF_IMM | XF_NF | XF_ONLY512, MC_T32, 32);
+    if (c == 0x39) return xform(EZ_EXT, wes, 0, false, XF_IMM | XF_TWO | XF_NO128, MC_T16, 16);
+    if (c == 0x3b) return xform(EZ_EXT, wes, 0, false, XF_IMM | XF_TWO | XF_ONLY512, MC_T32, 32);
+    if (c == 0x0f) return xform(EZ_ALIGNR, 1, 0, false, XF_IMM | XF_NF);
+    if (c == 0x00) return w ? xform(EZ_PERMQI, 8, 0, true, XF_IMM | XF_TWO | XF_NF | XF_NO128) : wud;
+    if (c == 0x03) return xform(EZ_VALIGN, wes, 0, true, XF_IMM | XF_NF);
+    if (c == 0x43) return xform(EZ_SHUFI, wes, 0, true, XF_IMM | XF_NF | XF_NO128);
     if (c == 0x25) return EForm{EZ_TERN, w ? 8u : 4u, 0, false, false, true, false};
     if (c == 0x3e || c == 0x3f) return EForm{EZ_CMP, w ? 2u : 1u, c & 1, false, false, false, true};
     if (c == 0x1e || c == 0x1f) return EForm{EZ_CMP, w ? 8u : 4u, c & 1, false, false, true, true};
@@ -104,12 +277,24 @@ __host__ __device__ inline EForm evex_form(u32 map, u32 c, u32 pp, u32 w) {
   return f;
 }
 
-// disp8 * N (SDM 2.7.5): full-vector forms scale by the vector length, a
-// broadcast memory operand (EVEX.b, or the broadcast instructions' element)
-// by the element size. vl: 16 / 32 / 64.
+// disp8 * N (SDM 2.7.5): by the memory operand's size class — the vector
+// length (full / full-mem), a half / quarter / eighth of it, 16 bytes — or,
+// for a broadcast memory operand (EVEX.b, or the broadcast instructions'
+// element), the element size. vl: 16 / 32 / 64.
 __host__ __device__ inline u32 evex_disp8_n(const EForm &f, u32 vl, u32 b) {
-  if (f.kind == EZ_BCAST || (b && f.bcastok)) return f.es;
-  return vl;
+  if (f.kind == EZ_BCAST) return f.es;
+  if (b && f.bcastok) return f.kind >= EZ_X ? f.ses : f.es;
+  switch (f.mc) {
+    case MC_HALF: return vl / 2;
+    case MC_QUARTER: return vl / 4;
+    case MC_EIGHTH: return vl / 8;
+    case MC_M128: return 16;
+    case MC_T8: return 8;
+    case MC_T16: return 16;
+    case MC_T32: return 32;
+    case MC_T1S: return f.es;
+    default: return vl;
+  }
 }
 
 // The VEX-encoded opmask instructions (0f 41-47 / 90-93 / 98 / 99, 0f 3a

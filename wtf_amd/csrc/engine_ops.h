@@ -350,13 +350,20 @@ __device__ __forceinline__ int decode(const IBytes &b, UOp &u, bool m32 = false)
     c = ib_at(b, pos++);
     const u32 emap = p0 & 7, ew = (p1 >> 7) & 1;
     vpp = p1 & 3;
-    ef = evex_form(emap, c, vpp, ew);
+    u32 digit = 0;
+    if (emap == 1 && c >= 0x71 && c <= 0x73) {  // the shift groups: the form is chosen by ModRM.reg
+      if (pos >= 15) return 2;
+      if (pos >= b.avail) return 1;
+      digit = (ib_at(b, pos) >> 3) & 7;
+    }
+    ef = evex_form(emap, c, vpp, ew, digit);
     // a legacy 66 / f2 / f3 / REX before EVEX or a reserved bit: #UD; maps
     // 1-3 and 5-6 (AVX512-FP16) are defined, the forms outside the subset
     // UNIMPLEMENTED (U36)
     const bool bad = p66 || u.rep || rex || (p0 & 8) || !(p1 & 4) || lock;
-    if (bad || !(emap == 1 || emap == 2 || emap == 3 || emap == 5 || emap == 6) || ef.kind == EZ_NONE) {
-      const bool ud = bad || emap == 0 || emap == 4 || emap == 7;
+    if (bad || !(emap == 1 || emap == 2 || emap == 3 || emap == 5 || emap == 6) || ef.kind == EZ_NONE ||
+        ef.kind == EZ_WUD) {
+      const bool ud = bad || emap == 0 || emap == 4 || emap == 7 || ef.kind == EZ_WUD;
       u.len = pos;
       u.op = ud ? O_UD : O_UNIMPL;
       u.supported = ud;
@@ -367,6 +374,7 @@ __device__ __forceinline__ int decode(const IBytes &b, UOp &u, bool m32 = false)
     vex = 1 | (ew << 2) | ((((~p1) >> 3) & 15) << 4) | (emap << 8) | EVX | (((p2 >> 5) & 3) << 18) |
           (((p2 >> 7) & 1) << 21) | (((p2 >> 4) & 1) << 22) | ((p2 & 7) << 23) | ((((~p2) >> 3) & 1) << 26) |
           ((((~p0) >> 4) & 1) << 27);  // bit 27: R' (moved into UOp::reg below)
+    if (ef.kind >= EZ_X) vex |= EVXX | (ef.kind >= EZ_Y ? EVXM : 0u);
   }
   u.rex = rex;
   const u32 rexw = (rex >> 3) & 1, rexr = (rex >> 2) & 1, rexx = (rex >> 1) & 1, rexb = rex & 1;
@@ -374,7 +382,7 @@ __device__ __forceinline__ int decode(const IBytes &b, UOp &u, bool m32 = false)
   if (vex & EVX) {
     smap = vex_map(vex);
     map2 = 1;
-    e = smap == 3 ? kSseModrmImm : kSseModrm;
+    e = (smap == 3 || (ef.fl & XF_IMM)) ? kSseModrmImm : kSseModrm;  // imm8: from the form table
   } else if (vex) {
     smap = vex_map(vex);
     map2 = 1;

@@ -477,6 +477,7 @@ __device__ __forceinline__ void mmx_put(wtfgpu_regs_t &F, u32 i, u64 v) {
 #include "engine_sse4.h"  // SSSE3 / SSE4.1 integer, AVX2 lane-crossing: s4_exec
 #include "engine_avx2x.h"  // FMA3, F16C, AVX2 gathers: ax_exec
 #include "engine_avx512.h"  // the EVEX subset and the opmask instructions: evex_exec, kop_exec
+#include "engine_avx512x.h"  // the EVEX integer shuffles, permutes, shifts and widenings (U49): evexx_exec
 namespace wtfgpu_dev {
 
 __device__ __noinline__ int mmx_exec(const Dev &P, Lane &L, const UOp &u, u64 nrip, u64 &next) {
@@ -810,6 +811,7 @@ __device__ __noinline__ int sse_exec(const Dev &P, Lane &L, const UOp &u, u64 nr
 __device__ __noinline__ int vex_exec(const Dev &P, Lane &L, const UOp &u, u64 nrip, u64 &next) {
   next = nrip;
   const u32 x = u.opreg, c = u.sub, pp = u.bsz, r3 = u.reg & 7, map = vex_map(x);
+  if (x & EVXX) return (x & EVXM) ? evexm_exec(P, L, u, nrip, next) : evexx_exec(P, L, u, nrip, next);  // engine_avx512x.h
   if (x & EVX) return evex_exec(P, L, u, nrip, next);                          // engine_avx512.h
   if (kop_bits(map, c, pp, 0) || kop_bits(map, c, pp, 1)) return kop_exec(P, L, u, nrip, next);  // W checked there
   if (fp_form(map, c, pp, true)) return fp_exec(P, L, u, nrip, next);  // its own VEX checks
