@@ -38,8 +38,11 @@ using namespace wtfgpu_dev;
 
 // What a queue owns (wtfgpu_select_queue): its stream and the scratch a call
 // on it stages through, so that work queued on one (a k_run slice) runs while
-// the host drives the other.
+// the host drives the other. The only home of per-queue state: the context
+// holds two of these and a pointer to the selected one (wtfgpu_ctx::q), so a
+// new member is declared here and nowhere else.
 struct QueueRes {
+  u32 index = 0;  // 0 or 1: picks the queue's set of warm LDS images (run_params)
   hipStream_t stream = nullptr;
   u8 *d_scratch = nullptr;
   u64 scratch_bytes = 0;
@@ -51,6 +54,7 @@ struct QueueRes {
   void *d_rtemp = nullptr;
   size_t rtemp_bytes = 0;
   u32 async_launches = 0;  // wtfgpu_run_async in flight (0 = none)
+  u8 rg_used = 2;          // its run in flight regroups (1), not (0), unmeasured (2): regroup_now
   // asynchronous plumbing (see ring_put / wtfgpu_prefetch_*): the pinned
   // upload ring, the prefetched exits / coverage entries, the event after the
   // queue's plumbing of its last run (another queue's work is ordered after it)
@@ -65,7 +69,6 @@ struct QueueRes {
 
 struct wtfgpu_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
   Dev P{};
   // pool
   u8 *d_pool = nullptr;
@@ -121,20 +124,13 @@ struct wtfgpu_ctx {
   std::vector<u8> h_pool;
   std::vector<u32> h_map;
   // misc
-  u64 *d_stat = nullptr;
   InitState *d_init = nullptr;
   wtfgpu_regs_t *d_init_full = nullptr;  // initial architectural state, copied per lane by k_restore
   wtfgpu_regs_t initial{};
   bool have_initial = false;
-  u8 *d_scratch = nullptr;
-  u8 *h_stage = nullptr;
-  u64 stage_bytes = 0;
-  // cross-wave regrouping (wtfgpu_run): sort keys, the lane order, radix-sort scratch
-  u32 *d_rkeys = nullptr, *d_rkeys2 = nullptr, *d_rlanes = nullptr, *d_perm = nullptr;
-  void *d_rtemp = nullptr;
-  size_t rtemp_bytes = 0;
-  u64 scratch_bytes = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // cross-wave regrouping (wtfgpu_run): the lane order, shared by the queues
+  // (each sorts its own lanes' part; keys and radix-sort scratch are per queue)
+  u32 *d_perm = nullptr;
   u64 regroup_steps = 1024;
   // regrouping pays only while lanes diverge from their wave neighbours:
   // regroup_now() measures both schedules (lanes retired per wave-step) and
@@ -149,20 +145,11 @@ struct wtfgpu_ctx {
   bool regroup_auto = true;
   double lps_sched[2] = {0, 0};  // lanes per wave-step, EMA: [0] fixed order, [1] regrouped
   u64 rg_runs = 0;
-  u8 rg_used[2] = {2, 2};  // per queue: its run in flight regroups (1), not (0), unmeasured (2)
   double nspi_sched[2] = {0, 0};  // run-to-completion runs: kernel ns per retired instruction, EMA
   u64 rg_sync_runs = 0;
-  u32 async_launches = 0;
-  u8 *h_ring = nullptr;
-  u64 ring_cap = 0, ring_off = 0;
-  wtfgpu_exit_t *d_exq = nullptr;
-  u64 exq_cap = 0;
-  u8 *d_pcov = nullptr;
-  hipEvent_t ev_pre = nullptr;
-  bool pre_valid = false;
-  // the current queue's resources live in the members above; the others here
+  // queue 1 is created at its first selection; every call works on *q
   QueueRes queues[2];
-  u32 cur_queue = 0;
+  QueueRes *q = &queues[0];  // the selected queue (wtfgpu_select_queue)
 };
 
 namespace {
@@ -191,13 +178,14 @@ void dfree(T *&p) {
 // (e.g. an asynchronous k_feed_scatter) and nothing synchronises the device,
 // so the other queue's k_run slice keeps running.
 int ensure_scratch(wtfgpu_ctx *c, u64 bytes) {
-  if (c->scratch_bytes >= bytes) return WTFGPU_OK;
-  const u64 want = std::max<u64>(std::max<u64>(bytes, 2 * c->scratch_bytes), 1ull << 20);
-  if (c->d_scratch) HIPCHK(hipFreeAsync(c->d_scratch, c->stream));
-  c->d_scratch = nullptr;
-  c->scratch_bytes = 0;
-  if (hipMallocAsync((void **)&c->d_scratch, want, c->stream) != hipSuccess) return WTFGPU_ERR_OOM;
-  c->scratch_bytes = want;
+  QueueRes &q = *c->q;
+  if (q.scratch_bytes >= bytes) return WTFGPU_OK;
+  const u64 want = std::max<u64>(std::max<u64>(bytes, 2 * q.scratch_bytes), 1ull << 20);
+  if (q.d_scratch) HIPCHK(hipFreeAsync(q.d_scratch, q.stream));
+  q.d_scratch = nullptr;
+  q.scratch_bytes = 0;
+  if (hipMallocAsync((void **)&q.d_scratch, want, q.stream) != hipSuccess) return WTFGPU_ERR_OOM;
+  q.scratch_bytes = want;
   return WTFGPU_OK;
 }
 
@@ -209,76 +197,30 @@ int ensure_scratch(wtfgpu_ctx *c, u64 bytes) {
 // after each synchronisation of the stream (wtfgpu_run_wait, or here when
 // full): no DMA still reads it then.
 u8 *ring_put(wtfgpu_ctx *c, const void *src, u64 bytes) {
+  QueueRes &q = *c->q;
   const u64 need = (bytes + 255) & ~255ull;
-  if (c->ring_off + need > c->ring_cap) {
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return nullptr;
-    c->ring_off = 0;
-    if (need > c->ring_cap) {
-      if (c->h_ring) (void)hipHostFree(c->h_ring);
-      c->h_ring = nullptr;
-      c->ring_cap = 0;
+  if (q.ring_off + need > q.ring_cap) {
+    if (hipStreamSynchronize(q.stream) != hipSuccess) return nullptr;
+    q.ring_off = 0;
+    if (need > q.ring_cap) {
+      if (q.h_ring) (void)hipHostFree(q.h_ring);
+      q.h_ring = nullptr;
+      q.ring_cap = 0;
       const u64 want = std::max<u64>(need * 2, 4ull << 20);
-      if (hipHostMalloc((void **)&c->h_ring, want, hipHostMallocDefault) != hipSuccess) return nullptr;
-      c->ring_cap = want;
+      if (hipHostMalloc((void **)&q.h_ring, want, hipHostMallocDefault) != hipSuccess) return nullptr;
+      q.ring_cap = want;
     }
   }
-  u8 *p = c->h_ring + c->ring_off;
+  u8 *p = q.h_ring + q.ring_off;
   if (src && bytes) memcpy(p, src, bytes);
-  c->ring_off += need;
+  q.ring_off += need;
   return p;
 }
 // the current queue's stream is idle: the ring may be reused from its start
-void ring_reset(wtfgpu_ctx *c) { c->ring_off = 0; }
+void ring_reset(wtfgpu_ctx *c) { c->q->ring_off = 0; }
 
-void queue_save(wtfgpu_ctx *c, QueueRes &q) {
-  q.stream = c->stream;
-  q.d_scratch = c->d_scratch;
-  q.scratch_bytes = c->scratch_bytes;
-  q.h_stage = c->h_stage;
-  q.stage_bytes = c->stage_bytes;
-  q.d_stat = c->d_stat;
-  q.ev0 = c->ev0;
-  q.ev1 = c->ev1;
-  q.d_rkeys = c->d_rkeys;
-  q.d_rkeys2 = c->d_rkeys2;
-  q.d_rlanes = c->d_rlanes;
-  q.d_rtemp = c->d_rtemp;
-  q.rtemp_bytes = c->rtemp_bytes;
-  q.async_launches = c->async_launches;
-  q.h_ring = c->h_ring;
-  q.ring_cap = c->ring_cap;
-  q.ring_off = c->ring_off;
-  q.d_exq = c->d_exq;
-  q.exq_cap = c->exq_cap;
-  q.d_pcov = c->d_pcov;
-  q.ev_pre = c->ev_pre;
-  q.pre_valid = c->pre_valid;
-}
-void queue_load(wtfgpu_ctx *c, const QueueRes &q) {
-  c->stream = q.stream;
-  c->d_scratch = q.d_scratch;
-  c->scratch_bytes = q.scratch_bytes;
-  c->h_stage = q.h_stage;
-  c->stage_bytes = q.stage_bytes;
-  c->d_stat = q.d_stat;
-  c->ev0 = q.ev0;
-  c->ev1 = q.ev1;
-  c->d_rkeys = q.d_rkeys;
-  c->d_rkeys2 = q.d_rkeys2;
-  c->d_rlanes = q.d_rlanes;
-  c->d_rtemp = q.d_rtemp;
-  c->rtemp_bytes = q.rtemp_bytes;
-  c->async_launches = q.async_launches;
-  c->h_ring = q.h_ring;
-  c->ring_cap = q.ring_cap;
-  c->ring_off = q.ring_off;
-  c->d_exq = q.d_exq;
-  c->exq_cap = q.exq_cap;
-  c->d_pcov = q.d_pcov;
-  c->ev_pre = q.ev_pre;
-  c->pre_valid = q.pre_valid;
-}
-int queue_create(QueueRes &q) {
+int queue_create(QueueRes &q, u32 index) {
+  q.index = index;
   HIPCHK(hipStreamCreateWithFlags(&q.stream, hipStreamNonBlocking));
   HIPCHK(hipEventCreate(&q.ev0));
   HIPCHK(hipEventCreate(&q.ev1));
@@ -286,17 +228,17 @@ int queue_create(QueueRes &q) {
   if (dalloc(&q.d_stat, STAT_N)) return WTFGPU_ERR_OOM;
   return WTFGPU_OK;
 }
-void regroup_free(u32 *&k, u32 *&k2, u32 *&l, void *&t, size_t &tb) {
-  dfree(k);
-  dfree(k2);
-  dfree(l);
-  if (t) (void)hipFree(t);
-  t = nullptr;
-  tb = 0;
+// a queue's regrouping buffers (sized by the lane count)
+void regroup_free(QueueRes &q) {
+  dfree(q.d_rkeys);
+  dfree(q.d_rkeys2);
+  dfree(q.d_rlanes);
+  dfree(q.d_rtemp);
+  q.rtemp_bytes = 0;
 }
 void queue_destroy(QueueRes &q) {
   if (q.stream) (void)hipStreamSynchronize(q.stream);
-  regroup_free(q.d_rkeys, q.d_rkeys2, q.d_rlanes, q.d_rtemp, q.rtemp_bytes);
+  regroup_free(q);
   dfree(q.d_stat);
   dfree(q.d_scratch);
   dfree(q.d_exq);
@@ -359,12 +301,97 @@ bool lanes_ok(wtfgpu_ctx *c, u32 first, u32 count) {
 
 template <typename T>
 int d2h(wtfgpu_ctx *c, T *dst, const T *src, u64 n) {
-  HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, c->q->stream));
   return WTFGPU_OK;
 }
 template <typename T>
 int h2d(wtfgpu_ctx *c, T *dst, const T *src, u64 n) {
-  HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, c->q->stream));
+  return WTFGPU_OK;
+}
+
+// ---- lane-list calls: a list of lanes (plus side arrays) -> the queue's
+// scratch -> one kernel over the list. Each call keeps its own argument
+// checks, in its own order (tests/test_gpu_abi_queues.py pins the return
+// codes), its own launch, and names its upload route at the stage_lanes call.
+
+// Every lane of the list is below the lane count. One branch-light pass: the
+// step thread hands over lists of a whole slice's lanes.
+bool lane_list_in_range(const wtfgpu_ctx *c, const u32 *lanes, u32 n) {
+  u32 bad = 0;
+  for (u32 i = 0; i < n; i++) bad |= (u32)(lanes[i] >= c->P.nlanes);
+  return !bad;
+}
+int check_lane_list(const wtfgpu_ctx *c, const u32 *lanes, u32 n) {
+  if (!c || !c->d_gpr || (n && !lanes) || !lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;
+  return WTFGPU_OK;
+}
+
+// A region of the scratch after the lane list: an input uploaded with the
+// list (src null: its place is kept, nothing is copied) or room the kernel
+// writes / the call fills itself. stage_lanes sets `off`.
+struct Side {
+  u64 bytes;
+  const void *src;
+  bool room;
+  u64 align;
+  u64 off;
+};
+Side side_in(const void *src, u64 bytes) { return Side{bytes, src, false, 256, 0}; }
+Side side_room(u64 bytes, u64 align = 256) { return Side{bytes, nullptr, true, align, 0}; }
+
+enum class Upload {
+  // Through the queue's pinned ring (ring_put), one DMA of the list and the
+  // inputs: the call returns without a wait, ordered before the queue's later
+  // work. For the calls that only change lane state; the step thread's
+  // overlap with the other queue's slice depends on it.
+  Ring,
+  // Straight from the caller's memory, a copy per array: for the calls that
+  // return data, which synchronise the queue before they return.
+  Direct,
+};
+
+// Lays the list (lanes null: no list) and the sides out in the current
+// queue's scratch, grown as needed, and queues the upload of the list and the
+// inputs on the queue's stream. Never waits for the stream (ring_put apart).
+int stage_lanes(wtfgpu_ctx *c, Upload route, const u32 *lanes, u32 n, Side *sides = nullptr, u32 nsides = 0) {
+  const u64 list = lanes ? (u64)n * 4 : 0;
+  u64 end = list, in_end = list;  // of everything, of the list and the inputs
+  for (u32 i = 0; i < nsides; i++) {
+    Side &s = sides[i];
+    s.off = (end + s.align - 1) & ~(s.align - 1);
+    end = s.off + s.bytes;
+    if (!s.room) in_end = end;
+  }
+  if (ensure_scratch(c, end)) return WTFGPU_ERR_OOM;
+  QueueRes &q = *c->q;
+  u8 *to = q.d_scratch;
+  if (route == Upload::Ring) {
+    to = ring_put(c, nullptr, in_end);
+    if (!to) return WTFGPU_ERR_OOM;
+  }
+  // Ring: host copies into the ring, then the one DMA; Direct: the DMAs themselves
+  const auto put = [&](u64 off, const void *src, u64 bytes) -> int {
+    if (!src || !bytes) return WTFGPU_OK;
+    if (route == Upload::Ring) memcpy(to + off, src, bytes);
+    else HIPCHK(hipMemcpyAsync(to + off, src, bytes, hipMemcpyHostToDevice, q.stream));
+    return WTFGPU_OK;
+  };
+  if (int rc = put(0, lanes, list)) return rc;
+  for (u32 i = 0; i < nsides; i++)
+    if (!sides[i].room)
+      if (int rc = put(sides[i].off, sides[i].src, sides[i].bytes)) return rc;
+  // (the place of an input without a source goes up as the ring holds it: its kernel gets no pointer to it)
+  if (route == Upload::Ring && in_end)
+    HIPCHK(hipMemcpyAsync(q.d_scratch, to, in_end, hipMemcpyHostToDevice, q.stream));
+  return WTFGPU_OK;
+}
+
+// The end of a Direct call that returns data: the region copied to the
+// caller, then the wait its caller relies on.
+int read_back(wtfgpu_ctx *c, void *dst, const Side &s) {
+  HIPCHK(hipMemcpyAsync(dst, c->q->d_scratch + s.off, s.bytes, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -382,7 +409,7 @@ int warm_clear(wtfgpu_ctx *c) {
 
 // Entries depend on the pool pages and the breakpoint set: cleared with them.
 int guc_clear(wtfgpu_ctx *c) {
-  if (c->d_guc) HIPCHK(hipMemsetAsync(c->d_guc, 0, (u64)(c->P.guc_mask + 1) * GUC_WORDS * 4, c->stream));
+  if (c->d_guc) HIPCHK(hipMemsetAsync(c->d_guc, 0, (u64)(c->P.guc_mask + 1) * GUC_WORDS * 4, c->q->stream));
   return warm_clear(c);
 }
 
@@ -427,21 +454,19 @@ int wtfgpu_create(int device, wtfgpu_ctx **out) {
       c->P.guc_mask = n - 1;
     }
   }
-  if (queue_create(c->queues[0]) || dalloc(&c->d_init, 1) || dalloc(&c->d_init_full, 1)) {
+  if (queue_create(c->queues[0], 0) || dalloc(&c->d_init, 1) || dalloc(&c->d_init_full, 1)) {
     wtfgpu_destroy(c);
     return WTFGPU_ERR_OOM;
   }
-  queue_load(c, c->queues[0]);
   *out = c;
   return WTFGPU_OK;
 }
 
-void *wtfgpu_stream(wtfgpu_ctx *c) { return c ? (void *)c->stream : nullptr; }
+void *wtfgpu_stream(wtfgpu_ctx *c) { return c ? (void *)c->q->stream : nullptr; }
 
 static void free_lanes(wtfgpu_ctx *c) {
   dfree(c->d_feedpos);  // sized by the lane count
   dfree(c->d_feedend);
-  c->d_feedpos = c->d_feedend = nullptr;
   c->P.feed_pos = nullptr;
   c->P.feed_end = nullptr;
   dfree(c->d_gpr);
@@ -466,9 +491,6 @@ static void free_lanes(wtfgpu_ctx *c) {
   dfree(c->d_trace);
   dfree(c->d_tracecnt);
   dfree(c->d_edgecnt);
-  c->d_trace = nullptr;
-  c->d_tracecnt = nullptr;
-  c->d_edgecnt = nullptr;
   c->P.trace = nullptr;
   c->P.trace_cnt = nullptr;
   c->P.edge_cnt = nullptr;
@@ -480,7 +502,6 @@ static void free_lanes(wtfgpu_ctx *c) {
     dfree(c->d_tn_ipos);
     dfree(c->d_tn_last);
     dfree(c->d_tn_mute);
-    c->d_tn_buf = nullptr, c->d_tn_pos = c->d_tn_cpos = c->d_tn_ipos = c->d_tn_last = nullptr, c->d_tn_mute = nullptr;
     c->tn_cap = 0;
     const TenetDev T{};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tn), &T, sizeof(T));
@@ -489,12 +510,7 @@ static void free_lanes(wtfgpu_ctx *c) {
   dfree(c->d_full);
   dfree(c->d_perm);
   // regrouping buffers are sized by the lane count: every queue's
-  regroup_free(c->d_rkeys, c->d_rkeys2, c->d_rlanes, c->d_rtemp, c->rtemp_bytes);
-  for (u32 q = 0; q < 2; q++)
-    if (q != c->cur_queue) {
-      QueueRes &Q = c->queues[q];
-      regroup_free(Q.d_rkeys, Q.d_rkeys2, Q.d_rlanes, Q.d_rtemp, Q.rtemp_bytes);
-    }
+  for (QueueRes &q : c->queues) regroup_free(q);
   dfree(c->d_covrip);
   dfree(c->d_covgen);
   dfree(c->d_lanegen);
@@ -517,8 +533,6 @@ int wtfgpu_destroy(wtfgpu_ctx *c) {
   dfree(c->d_bp);
   dfree(c->d_actkeys);
   dfree(c->d_act);
-  dfree(c->d_feedpos);
-  dfree(c->d_feedend);
   dfree(c->d_feeddata);
   dfree(c->d_codekeys);
   dfree(c->d_codeslot);
@@ -526,7 +540,6 @@ int wtfgpu_destroy(wtfgpu_ctx *c) {
   dfree(c->d_covshadow);
   dfree(c->d_init);
   dfree(c->d_init_full);
-  queue_save(c, c->queues[c->cur_queue]);
   for (QueueRes &q : c->queues) queue_destroy(q);
   delete c;
   return WTFGPU_OK;
@@ -556,13 +569,13 @@ int wtfgpu_load_pool(wtfgpu_ctx *c, const uint64_t *gpfns, const uint8_t *pages,
   }
   if (dalloc(&c->d_pfnmap, maplen)) return WTFGPU_ERR_OOM;
   if (dalloc(&c->d_ptbits, (maplen + 31) / 32)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemsetAsync(c->d_pool, 0, WTFGPU_PAGE_SIZE, c->stream));
+  HIPCHK(hipMemsetAsync(c->d_pool, 0, WTFGPU_PAGE_SIZE, c->q->stream));
   if (npages)
     HIPCHK(hipMemcpyAsync(c->d_pool + WTFGPU_PAGE_SIZE, pages, npages * WTFGPU_PAGE_SIZE, hipMemcpyHostToDevice,
-                          c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_pfnmap, map.data(), maplen * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_ptbits, 0, (maplen + 31) / 32 * 4, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+                          c->q->stream));
+  HIPCHK(hipMemcpyAsync(c->d_pfnmap, map.data(), maplen * 4, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_ptbits, 0, (maplen + 31) / 32 * 4, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
 
   c->npool = npages;
   c->h_pool.assign(pages, pages + npages * WTFGPU_PAGE_SIZE);
@@ -572,9 +585,9 @@ int wtfgpu_load_pool(wtfgpu_ctx *c, const uint64_t *gpfns, const uint8_t *pages,
   c->P.pfn_map_len = maplen;
   c->P.npool = npages;
   c->P.ptbits = c->d_ptbits;
-  if (c->d_tlbok) HIPCHK(hipMemsetAsync(c->d_tlbok, 0, (u64)c->P.nlanes * 4, c->stream));  // old page pointers
+  if (c->d_tlbok) HIPCHK(hipMemsetAsync(c->d_tlbok, 0, (u64)c->P.nlanes * 4, c->q->stream));  // old page pointers
   if (guc_clear(c)) return WTFGPU_ERR_HIP;
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   if (c->have_initial) return mark_pt_pages(c);
   return WTFGPU_OK;
 }
@@ -631,22 +644,22 @@ int wtfgpu_alloc_lanes(wtfgpu_ctx *c, uint32_t nlanes, uint32_t overlay_pages, u
   }
   if (rc) return WTFGPU_ERR_OOM;
   std::vector<u32> idle(N, WTFGPU_EXIT_IDLE);
-  HIPCHK(hipMemcpyAsync(c->d_status, idle.data(), N * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_ovcount, 0, N * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_lflags, 0, N * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_tlbok, 0, N * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_rdseed, 0, N * 8, c->stream));  // CpuState_t::Seed = 0 (globals.h:1084)
-  HIPCHK(hipMemsetAsync(c->d_icount, 0, N * 8, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_nbytes, 0, N * 8, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_exinfo, 0, N * sizeof(ExitInfo), c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_status, idle.data(), N * 4, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_ovcount, 0, N * 4, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_lflags, 0, N * 4, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_tlbok, 0, N * 4, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_rdseed, 0, N * 8, c->q->stream));  // CpuState_t::Seed = 0 (globals.h:1084)
+  HIPCHK(hipMemsetAsync(c->d_icount, 0, N * 8, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_nbytes, 0, N * 8, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_exinfo, 0, N * sizeof(ExitInfo), c->q->stream));
   if (cov_entries) {
-    HIPCHK(hipMemsetAsync(c->d_covgen, 0, N * cov_entries * 4, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_covgen, 0, N * cov_entries * 4, c->q->stream));
     std::vector<u32> one(N, 1);  // generation 1: every entry (0) is empty
-    HIPCHK(hipMemcpyAsync(c->d_lanegen, one.data(), N * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_covcnt, 0, N * 4, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_covovf, 0, N * 4, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_lanegen, one.data(), N * 4, hipMemcpyHostToDevice, c->q->stream));
+    HIPCHK(hipMemsetAsync(c->d_covcnt, 0, N * 4, c->q->stream));
+    HIPCHK(hipMemsetAsync(c->d_covovf, 0, N * 4, c->q->stream));
   }
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   Dev &P = c->P;
   P.nlanes = nlanes;
   P.K = overlay_pages;
@@ -680,7 +693,7 @@ int wtfgpu_alloc_lanes(wtfgpu_ctx *c, uint32_t nlanes, uint32_t overlay_pages, u
   P.cov_cnt = c->d_covcnt;
   P.cov_overflow = c->d_covovf;
   P.H = cov_entries;
-  P.stat = c->d_stat;
+  P.stat = c->q->d_stat;
   if (P.edges) return wtfgpu_set_edges(c, 1);  // the counters follow the lane count
   return WTFGPU_OK;
 }
@@ -718,8 +731,8 @@ static int mark_pt_pages(wtfgpu_ctx *c) {
       work.push_back({(e & 0x000ffffffffff000ull) >> 12, level - 1});
     }
   }
-  HIPCHK(hipMemcpyAsync(c->d_ptbits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_ptbits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -729,11 +742,11 @@ int wtfgpu_set_initial_state(wtfgpu_ctx *c, const wtfgpu_regs_t *regs) {
   c->initial = *regs;
   c->have_initial = true;
   c->P.cr3_0 = regs->cr3;
-  if (c->d_tlbok) HIPCHK(hipMemsetAsync(c->d_tlbok, 0, (u64)c->P.nlanes * 4, c->stream));  // page-table pages change
+  if (c->d_tlbok) HIPCHK(hipMemsetAsync(c->d_tlbok, 0, (u64)c->P.nlanes * 4, c->q->stream));  // page-table pages change
   const InitState s = make_init(*regs);
-  HIPCHK(hipMemcpyAsync(c->d_init, &s, sizeof(s), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_init_full, regs, sizeof(*regs), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_init, &s, sizeof(s), hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemcpyAsync(c->d_init_full, regs, sizeof(*regs), hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return mark_pt_pages(c);
 }
 
@@ -757,7 +770,7 @@ int wtfgpu_set_breakpoints(wtfgpu_ctx *c, const uint64_t *gvas, uint32_t n) {
   c->P.bp_mask = 0;
   if (guc_clear(c)) return WTFGPU_ERR_HIP;  // shared entries carry the breakpoint flag
   if (n == 0) {
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->q->stream));
     return WTFGPU_OK;
   }
   const u32 sz = table_size(n);
@@ -768,8 +781,8 @@ int wtfgpu_set_breakpoints(wtfgpu_ctx *c, const uint64_t *gvas, uint32_t n) {
     t[h] = gvas[i];
   }
   if (dalloc(&c->d_bp, sz)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_bp, t.data(), sz * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_bp, t.data(), sz * 8, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   c->P.bp_keys = c->d_bp;
   c->P.bp_mask = sz - 1;
   return WTFGPU_OK;
@@ -782,7 +795,7 @@ int wtfgpu_set_breakpoint_actions(wtfgpu_ctx *c, const wtfgpu_bp_action_t *acts,
     if (acts[i].kind == WTFGPU_BPACT_STOP_ARGS && acts[i].value > 6) return WTFGPU_ERR_INVALID;
   }
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   dfree(c->d_actkeys);
   dfree(c->d_act);
   c->P.act_keys = nullptr;
@@ -800,9 +813,9 @@ int wtfgpu_set_breakpoint_actions(wtfgpu_ctx *c, const wtfgpu_bp_action_t *acts,
     a[h] = acts[i];
   }
   if (dalloc(&c->d_actkeys, sz) || dalloc(&c->d_act, sz)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_actkeys, t.data(), sz * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_act, a.data(), sz * sizeof(wtfgpu_bp_action_t), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_actkeys, t.data(), sz * 8, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemcpyAsync(c->d_act, a.data(), sz * sizeof(wtfgpu_bp_action_t), hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   c->P.act_keys = c->d_actkeys;
   c->P.act = c->d_act;
   c->P.act_mask = sz - 1;
@@ -815,7 +828,7 @@ int wtfgpu_set_feed(wtfgpu_ctx *c, uint32_t first, uint32_t count, const uint64_
   for (u32 i = 0; i < count; i++)
     if (offsets[i + 1] < offsets[i] || offsets[i + 1] > nbytes) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   const u64 N = c->P.nlanes;
   if (!c->d_feedpos) {
     if (dalloc(&c->d_feedpos, N) || dalloc(&c->d_feedend, N)) return WTFGPU_ERR_OOM;
@@ -826,7 +839,6 @@ int wtfgpu_set_feed(wtfgpu_ctx *c, uint32_t first, uint32_t count, const uint64_
   c->feed_stride = 0;  // packed layout (per-lane regions: wtfgpu_set_feed_lanes)
   if (nbytes > c->feed_cap) {
     dfree(c->d_feeddata);
-    c->d_feeddata = nullptr;
     c->feed_cap = 0;
     if (dalloc(&c->d_feeddata, nbytes)) return WTFGPU_ERR_OOM;
     c->feed_cap = nbytes;
@@ -837,17 +849,17 @@ int wtfgpu_set_feed(wtfgpu_ctx *c, uint32_t first, uint32_t count, const uint64_
     pos[i] = has ? offsets[i] : ~0ull;
     end[i] = offsets[i + 1];
   }
-  if (nbytes) HIPCHK(hipMemcpyAsync(c->d_feeddata, bytes, nbytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_feedpos + first, pos.data(), count * 8ull, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_feedend + first, end.data(), count * 8ull, hipMemcpyHostToDevice, c->stream));
+  if (nbytes) HIPCHK(hipMemcpyAsync(c->d_feeddata, bytes, nbytes, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemcpyAsync(c->d_feedpos + first, pos.data(), count * 8ull, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemcpyAsync(c->d_feedend + first, end.data(), count * 8ull, hipMemcpyHostToDevice, c->q->stream));
   c->P.feed_pos = c->d_feedpos;
   c->P.feed_end = c->d_feedend;
   c->P.feed_data = c->d_feeddata;
   if (c->ins_on && count) {
-    k_insert<<<(count + 63) / 64, 64, 0, c->stream>>>(c->P, c->ins, nullptr, first, count);
+    k_insert<<<(count + 63) / 64, 64, 0, c->q->stream>>>(c->P, c->ins, nullptr, first, count);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -887,11 +899,11 @@ int wtfgpu_set_code_pages(wtfgpu_ctx *c, const uint64_t *vpns, uint32_t n) {
   if (dalloc(&c->d_codekeys, sz) || dalloc(&c->d_codeslot, sz) || dalloc(&c->d_covmap, (u64)n * WTFGPU_PAGE_SIZE) ||
       dalloc(&c->d_covshadow, (u64)n * WTFGPU_PAGE_SIZE))
     return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_codekeys, keys.data(), sz * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_codeslot, slots.data(), sz * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_covmap, 0, (u64)n * WTFGPU_PAGE_SIZE, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_covshadow, 0, (u64)n * WTFGPU_PAGE_SIZE, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_codekeys, keys.data(), sz * 8, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemcpyAsync(c->d_codeslot, slots.data(), sz * 4, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_covmap, 0, (u64)n * WTFGPU_PAGE_SIZE, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_covshadow, 0, (u64)n * WTFGPU_PAGE_SIZE, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   if (int rc = warm_clear(c)) return rc;  // images carry UC_COVERED
   c->P.cov_shadow = c->d_covshadow;
   c->P.code_keys = c->d_codekeys;
@@ -905,41 +917,38 @@ int wtfgpu_restore(wtfgpu_ctx *c, uint32_t first, uint32_t count) {
   if (!lanes_ok(c, first, count) || !c->have_initial) return WTFGPU_ERR_STATE;
   if (count == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  k_restore<<<(count + 255) / 256, 256, 0, c->stream>>>(c->P, c->d_init, c->d_init_full, c->d_full, first, count);
+  k_restore<<<(count + 255) / 256, 256, 0, c->q->stream>>>(c->P, c->d_init, c->d_init_full, c->d_full, first, count);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
 int wtfgpu_restore_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n) {
-  if (!c || !c->d_gpr || !c->have_initial || (n && !lanes)) return WTFGPU_ERR_INVALID;
+  if (!c || !c->have_initial) return WTFGPU_ERR_INVALID;
+  if (int rc = check_lane_list(c, lanes, n)) return rc;
   if (n == 0) return WTFGPU_OK;
-  for (u32 i = 0; i < n; i++)
-    if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  // queued without a wait (ordered before the queue's later work, see ring_put)
-  const u8 *st = ring_put(c, lanes, (u64)n * 4);
-  if (!st || ensure_scratch(c, (u64)n * 4)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, st, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  k_restore_list<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, c->d_init, c->d_init_full, c->d_full,
-                                                         (const u32 *)c->d_scratch, n);
+  if (int rc = stage_lanes(c, Upload::Ring, lanes, n)) return rc;
+  k_restore_list<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, c->d_init, c->d_init_full, c->d_full,
+                                                         (const u32 *)c->q->d_scratch, n);
   HIPCHK(hipGetLastError());
   return WTFGPU_OK;
 }
 
 int wtfgpu_set_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, const uint64_t *offsets,
                           const uint8_t *has_feed, const uint8_t *bytes, uint64_t nbytes) {
-  if (!c || !c->d_gpr || (n && (!lanes || !offsets)) || (nbytes && !bytes)) return WTFGPU_ERR_INVALID;
-  {  // one branch-light pass: lanes in range, offsets ascending within the bytes
+  if (!c || !c->d_gpr || (n && (!lanes || !offsets)) || (nbytes && !bytes) || !lane_list_in_range(c, lanes, n))
+    return WTFGPU_ERR_INVALID;
+  {  // one branch-light pass: offsets ascending within the bytes
     u32 bad = 0;
-    for (u32 i = 0; i < n; i++)
-      bad |= (u32)(lanes[i] >= c->P.nlanes) | (u32)(offsets[i + 1] < offsets[i]) | (u32)(offsets[i + 1] > nbytes);
+    for (u32 i = 0; i < n; i++) bad |= (u32)(offsets[i + 1] < offsets[i]) | (u32)(offsets[i + 1] > nbytes);
     if (bad) return WTFGPU_ERR_INVALID;
   }
   if (n == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   const u64 N = c->P.nlanes;
-  if (!c->d_feedpos || c->feed_stride == 0) HIPCHK(hipDeviceSynchronize());  // first use: buffers change under every queue
+  // first use: buffers change under every queue
+  if (!c->d_feedpos || c->feed_stride == 0) HIPCHK(hipDeviceSynchronize());
   if (!c->d_feedpos) {
     if (dalloc(&c->d_feedpos, N) || dalloc(&c->d_feedend, N)) return WTFGPU_ERR_OOM;
     std::vector<u64> none(N, ~0ull);
@@ -948,7 +957,6 @@ int wtfgpu_set_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, cons
   if (c->feed_stride == 0) {  // switch to per-lane regions (a packed feed's lanes are finished by now)
     const u64 stride = 16384;
     dfree(c->d_feeddata);
-    c->d_feeddata = nullptr;
     c->feed_cap = 0;
     if (dalloc(&c->d_feeddata, N * stride)) return WTFGPU_ERR_OOM;
     c->feed_cap = N * stride;
@@ -957,19 +965,14 @@ int wtfgpu_set_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, cons
   // one staging upload of the lane list, the offsets and the flags (the
   // scatter derives each lane's length, position and end), one of the bytes
   // (straight from the caller's buffer: pinned memory DMAs), then one scatter
-  const u64 o_off = ((u64)n * 4 + 255) & ~255ull, o_has = (o_off + (u64)(n + 1) * 8 + 255) & ~255ull,
-            o_data = (o_has + n + 255) & ~255ull;
-  if (ensure_scratch(c, o_data + nbytes)) return WTFGPU_ERR_OOM;
-  u8 *stage = ring_put(c, nullptr, o_data);  // (see ring_put: no wait for the queue)
-  if (!stage) return WTFGPU_ERR_OOM;
-  memcpy(stage, lanes, (u64)n * 4);
-  memcpy(stage + o_off, offsets, (u64)(n + 1) * 8);
-  if (has_feed) memcpy(stage + o_has, has_feed, n);
-  HIPCHK(hipMemcpyAsync(c->d_scratch, stage, o_data, hipMemcpyHostToDevice, c->stream));
-  if (nbytes) HIPCHK(hipMemcpyAsync(c->d_scratch + o_data, bytes, nbytes, hipMemcpyHostToDevice, c->stream));
-  k_feed_scatter<<<n, 128, 0, c->stream>>>(c->d_feeddata, c->feed_stride, (const u32 *)c->d_scratch,
-                                           (const u64 *)(c->d_scratch + o_off), has_feed ? c->d_scratch + o_has : nullptr,
-                                           n, c->d_scratch + o_data, c->d_feedpos, c->d_feedend);
+  Side s[] = {side_in(offsets, (u64)(n + 1) * 8), side_in(has_feed, n), side_room(nbytes)};
+  const Side &off = s[0], &has = s[1], &data = s[2];
+  if (int rc = stage_lanes(c, Upload::Ring, lanes, n, s, 3)) return rc;
+  u8 *const S = c->q->d_scratch;
+  if (nbytes) HIPCHK(hipMemcpyAsync(S + data.off, bytes, nbytes, hipMemcpyHostToDevice, c->q->stream));
+  k_feed_scatter<<<n, 128, 0, c->q->stream>>>(c->d_feeddata, c->feed_stride, (const u32 *)S,
+                                              (const u64 *)(S + off.off), has_feed ? S + has.off : nullptr, n,
+                                              S + data.off, c->d_feedpos, c->d_feedend);
   HIPCHK(hipGetLastError());
   // no wait: the queue's later work (its k_run slice) is ordered after the
   // scatter, and the next call on this queue synchronises first
@@ -977,7 +980,7 @@ int wtfgpu_set_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, cons
   c->P.feed_end = c->d_feedend;
   c->P.feed_data = c->d_feeddata;
   if (c->ins_on) {  // the declared insert of the listed lanes, ordered after the scatter
-    k_insert<<<(n + 63) / 64, 64, 0, c->stream>>>(c->P, c->ins, (const u32 *)c->d_scratch, 0, n);
+    k_insert<<<(n + 63) / 64, 64, 0, c->q->stream>>>(c->P, c->ins, (const u32 *)c->q->d_scratch, 0, n);
     HIPCHK(hipGetLastError());
   }
   return WTFGPU_OK;
@@ -995,7 +998,7 @@ int wtfgpu_read_gprs(wtfgpu_ctx *c, uint32_t first, uint32_t count, uint64_t *ou
   rc |= d2h(c, tmp.data() + (u64)16 * count, c->d_rip + first, count);
   rc |= d2h(c, tmp.data() + (u64)17 * count, c->d_rflags + first, count);
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   for (u64 l = 0; l < count; l++)
     for (int i = 0; i < 18; i++) out18[l * 18 + i] = tmp[(u64)i * count + l];
   return WTFGPU_OK;
@@ -1013,7 +1016,7 @@ int wtfgpu_write_gprs(wtfgpu_ctx *c, uint32_t first, uint32_t count, const uint6
   rc |= h2d(c, c->d_rip + first, tmp.data() + (u64)16 * count, count);
   rc |= h2d(c, c->d_rflags + first, tmp.data() + (u64)17 * count, count);
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -1030,7 +1033,7 @@ int wtfgpu_read_regs(wtfgpu_ctx *c, uint32_t first, uint32_t count, wtfgpu_regs_
   rc |= d2h(c, gsb.data(), c->d_gsb + first, count);
   rc |= d2h(c, sys.data(), c->d_sys + first, count);
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   for (u64 l = 0; l < count; l++) {
     wtfgpu_regs_t &r = out[l];
     for (int i = 0; i < 16; i++) r.gpr[i] = g[l * 18 + i];
@@ -1073,9 +1076,9 @@ int wtfgpu_write_regs(wtfgpu_ctx *c, uint32_t first, uint32_t count, const wtfgp
   rc |= h2d(c, c->d_fsb + first, fsb.data(), count);
   rc |= h2d(c, c->d_gsb + first, gsb.data(), count);
   rc |= h2d(c, c->d_sys + first, sys.data(), count);
-  if (c->d_tlbok) HIPCHK(hipMemsetAsync(c->d_tlbok + first, 0, (u64)count * 4, c->stream));
+  if (c->d_tlbok) HIPCHK(hipMemsetAsync(c->d_tlbok + first, 0, (u64)count * 4, c->q->stream));
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -1086,29 +1089,22 @@ int wtfgpu_read_exits(wtfgpu_ctx *c, uint32_t first, uint32_t count, wtfgpu_exit
   // packed on the device, one copy back
   const u64 bytes = (u64)count * sizeof(wtfgpu_exit_t);
   if (ensure_scratch(c, bytes)) return WTFGPU_ERR_OOM;
-  k_pack_exits<<<(count + 255) / 256, 256, 0, c->stream>>>(c->P, first, count, (wtfgpu_exit_t *)c->d_scratch);
+  k_pack_exits<<<(count + 255) / 256, 256, 0, c->q->stream>>>(c->P, first, count, (wtfgpu_exit_t *)c->q->d_scratch);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, c->d_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->q->d_scratch, bytes, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
 static int set_status_list(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32_t status, const uint8_t *skip) {
-  if (!c || !c->d_status || (n && !lanes)) return WTFGPU_ERR_INVALID;
+  if (!c || !c->d_status || (n && !lanes) || !lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;
   if (n == 0) return WTFGPU_OK;
-  for (u32 i = 0; i < n; i++)
-    if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
   // lane list (+ skip flags) -> scratch, one scatter kernel: no whole-array round trips
-  // queued without a wait (ordered before the queue's later work, see ring_put)
-  const u64 o_skip = ((u64)n * 4 + 255) & ~255ull;
-  u8 *st = ring_put(c, nullptr, o_skip + n);
-  if (!st || ensure_scratch(c, o_skip + n)) return WTFGPU_ERR_OOM;
-  memcpy(st, lanes, (u64)n * 4);
-  if (skip) memcpy(st + o_skip, skip, n);
-  HIPCHK(hipMemcpyAsync(c->d_scratch, st, skip ? o_skip + n : (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  k_set_status<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, n, status,
-                                                      skip ? c->d_scratch + o_skip : nullptr);
+  Side sk = side_in(skip, n);
+  if (int rc = stage_lanes(c, Upload::Ring, lanes, n, &sk, 1)) return rc;
+  k_set_status<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, (const u32 *)c->q->d_scratch, n, status,
+                                                          skip ? c->q->d_scratch + sk.off : nullptr);
   HIPCHK(hipGetLastError());
   return WTFGPU_OK;
 }
@@ -1128,15 +1124,16 @@ int wtfgpu_stop(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32_t statu
 
 // Regrouping buffers of the current queue (sized by the lane count).
 static int regroup_buffers(wtfgpu_ctx *c) {
-  if (c->d_rkeys) return WTFGPU_OK;
+  QueueRes &q = *c->q;
+  if (q.d_rkeys) return WTFGPU_OK;
   const u64 N = c->P.nlanes;
   if (!c->d_perm && dalloc(&c->d_perm, N)) return WTFGPU_ERR_OOM;
-  if (dalloc(&c->d_rkeys, N) || dalloc(&c->d_rkeys2, N) || dalloc(&c->d_rlanes, N)) return WTFGPU_ERR_OOM;
+  if (dalloc(&q.d_rkeys, N) || dalloc(&q.d_rkeys2, N) || dalloc(&q.d_rlanes, N)) return WTFGPU_ERR_OOM;
   size_t bytes = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, c->d_rkeys, c->d_rkeys2, c->d_rlanes, c->d_perm, (int)N, 0,
-                                            24, c->stream));
-  HIPCHK(hipMalloc(&c->d_rtemp, bytes));
-  c->rtemp_bytes = bytes;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, q.d_rkeys, q.d_rkeys2, q.d_rlanes, c->d_perm, (int)N, 0, 24,
+                                            q.stream));
+  HIPCHK(hipMalloc(&q.d_rtemp, bytes));
+  q.rtemp_bytes = bytes;
   return WTFGPU_OK;
 }
 
@@ -1144,7 +1141,7 @@ static int regroup_buffers(wtfgpu_ctx *c) {
 static Dev run_params(wtfgpu_ctx *c, bool regroup) {
   Dev Q = c->P;
   Q.perm = regroup ? c->d_perm : nullptr;
-  Q.stat = c->d_stat;
+  Q.stat = c->q->d_stat;
   // warm-started LDS uop caches (WTFGPU_WARM=0: every launch starts empty)
   const char *w = getenv("WTFGPU_WARM");
   if (!(w && atoi(w) == 0)) {
@@ -1164,7 +1161,7 @@ static Dev run_params(wtfgpu_ctx *c, bool regroup) {
         c->d_warm = nullptr;
       }
     }
-    Q.warm = c->d_warm ? c->d_warm + (u64)(c->cur_queue % UC_QUEUES) * UC_IMAGE_BYTES * c->warm_n : nullptr;
+    Q.warm = c->d_warm ? c->d_warm + (u64)(c->q->index % UC_QUEUES) * UC_IMAGE_BYTES * c->warm_n : nullptr;
     Q.warm_n = c->warm_n;
   } else {
     Q.warm = nullptr;
@@ -1177,7 +1174,7 @@ static Dev run_params(wtfgpu_ctx *c, bool regroup) {
 // (regrouping must win by kMargin: its sorts and shorter launches cost time a
 // wave-step count does not show), probing the other every kProbe-th run.
 static u64 regroup_now(wtfgpu_ctx *c, u32 count) {
-  c->rg_used[c->cur_queue & 1] = 2;  // not a measured choice
+  c->q->rg_used = 2;  // not a measured choice
   if (!c->regroup_steps || count < 2 * c->P.lpw) return 0;
   if (!c->regroup_auto) return c->regroup_steps;
   static constexpr double kMargin = 1.1;
@@ -1190,7 +1187,7 @@ static u64 regroup_now(wtfgpu_ctx *c, u32 count) {
     on = c->lps_sched[1] > kMargin * c->lps_sched[0];
     if (i % kProbe == kProbe - 1) on = !on;
   }
-  c->rg_used[c->cur_queue & 1] = on;
+  c->q->rg_used = on;
   return on ? c->regroup_steps : 0;
 }
 // The same choice for a synchronous run to completion, by kernel time per
@@ -1218,7 +1215,7 @@ static void regroup_observe_timed(wtfgpu_ctx *c, int used, double ms, u64 retire
   e = e == 0 ? v : 0.75 * e + 0.25 * v;
 }
 static void regroup_observe(wtfgpu_ctx *c, u64 group_steps, u64 retired) {
-  const u8 used = c->rg_used[c->cur_queue & 1];
+  const u8 used = c->q->rg_used;
   if (used > 1 || group_steps < 64) return;
   const double lps = (double)retired / (double)group_steps;
   double &e = c->lps_sched[used];
@@ -1228,16 +1225,17 @@ static void regroup_observe(wtfgpu_ctx *c, u64 group_steps, u64 retired) {
 // One k_run launch of `steps` wave-steps over [first, first + count), after
 // the regrouping sort when on.
 static int launch_chunk(wtfgpu_ctx *c, const Dev &Q, u32 first, u32 count, u64 steps, bool regroup) {
+  QueueRes &q = *c->q;
   const u32 hwaves = (count + c->P.lpw - 1) / c->P.lpw;
   if (regroup) {
-    HIPCHK(hipMemsetAsync(c->d_stat + 2, 0, 16, c->stream));  // running lanes: this launch's (2: after, 3: before)
-    k_regroup_keys<<<(count + 255) / 256, 256, 0, c->stream>>>(Q, first, count, c->d_rkeys, c->d_rlanes);
+    HIPCHK(hipMemsetAsync(q.d_stat + 2, 0, 16, q.stream));  // running lanes: this launch's (2: after, 3: before)
+    k_regroup_keys<<<(count + 255) / 256, 256, 0, q.stream>>>(Q, first, count, q.d_rkeys, q.d_rlanes);
     HIPCHK(hipGetLastError());
-    size_t bytes = c->rtemp_bytes;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(c->d_rtemp, bytes, c->d_rkeys, c->d_rkeys2, c->d_rlanes,
-                                              c->d_perm + first, (int)count, 0, 24, c->stream));
+    size_t bytes = q.rtemp_bytes;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(q.d_rtemp, bytes, q.d_rkeys, q.d_rkeys2, q.d_rlanes, c->d_perm + first,
+                                              (int)count, 0, 24, q.stream));
   }
-  k_run<<<(hwaves + 3) / 4, 256, 0, c->stream>>>(Q, first, count, steps);
+  k_run<<<(hwaves + 3) / 4, 256, 0, q.stream>>>(Q, first, count, steps);
   HIPCHK(hipGetLastError());
   return WTFGPU_OK;
 }
@@ -1265,10 +1263,45 @@ static void print_stamps(const u64 *s) {
 #endif
 }
 
+// Up to `group` k_run launches of `chunk` wave-steps each, until `done`
+// reaches max_steps, queued between the queue's ev0 and ev1 over zeroed
+// statistics. Nothing waits.
+static int queue_launches(wtfgpu_ctx *c, const Dev &Q, u32 first, u32 count, u64 chunk, u64 max_steps, u64 group,
+                          bool regroup, u64 &done, u32 &launches) {
+  QueueRes &q = *c->q;
+  HIPCHK(hipMemsetAsync(q.d_stat, 0, STAT_N * 8, q.stream));
+  HIPCHK(hipEventRecord(q.ev0, q.stream));
+  for (launches = 0; launches < group && done < max_steps; launches++) {
+    const u64 steps = std::min<u64>(chunk, max_steps - done);
+    if (int rc = launch_chunk(c, Q, first, count, steps, regroup)) return rc;
+    done += steps;
+  }
+  HIPCHK(hipEventRecord(q.ev1, q.stream));
+  return WTFGPU_OK;
+}
+
+// The statistics of the launches queued last, added to `st`, after a wait for
+// them; `running`: the lanes still running after the last launch.
+static int collect_stats(wtfgpu_ctx *c, u32 launches, wtfgpu_run_stats_t &st, u64 &running) {
+  QueueRes &q = *c->q;
+  u64 s[STAT_N];
+  HIPCHK(hipMemcpyAsync(s, q.d_stat, sizeof(s), hipMemcpyDeviceToHost, q.stream));
+  HIPCHK(hipStreamSynchronize(q.stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, q.ev0, q.ev1));
+  st.kernel_launches += launches;
+  st.group_steps += s[0];
+  st.lane_retired += s[1];
+  st.kernel_ms += ms;
+  running = s[2];
+  print_stamps(s);
+  return WTFGPU_OK;
+}
+
 int wtfgpu_run(wtfgpu_ctx *c, uint32_t first, uint32_t count, uint64_t max_steps, wtfgpu_run_stats_t *stats) {
   if (!lanes_ok(c, first, count) || (first % c->P.lpw)) return WTFGPU_ERR_INVALID;
   if (!c->P.pool) return WTFGPU_ERR_STATE;
-  if (c->async_launches) return WTFGPU_ERR_STATE;  // wtfgpu_run_wait first
+  if (c->q->async_launches) return WTFGPU_ERR_STATE;  // wtfgpu_run_wait first
   HIPCHK(hipSetDevice(c->device));
   wtfgpu_run_stats_t st{};
   u64 chunk = 1ull << 20;  // wave-steps per launch: keeps every launch short
@@ -1288,33 +1321,14 @@ int wtfgpu_run(wtfgpu_ctx *c, uint32_t first, uint32_t count, uint64_t max_steps
   // launches per host synchronisation: regrouped chunks are short, so a
   // group of them is queued at once (one stats read-back per group)
   const u32 group = regroup ? (u32)std::max<u64>(1, 4096 / regroup) : 1;
-  u64 done = 0;
-  float ms_total = 0;
-  for (;;) {
-    HIPCHK(hipMemsetAsync(c->d_stat, 0, STAT_N * 8, c->stream));
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
+  u64 done = 0, running = 0;
+  do {  // a statistics read-back per group; ends when no lane is running
     u32 k = 0;
-    for (; k < group && done < max_steps; k++) {
-      const u64 steps = std::min<u64>(chunk, max_steps - done);
-      if (int rc = launch_chunk(c, Q, first, count, steps, regroup != 0)) return rc;
-      done += steps;
-    }
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    u64 s[STAT_N];
-    HIPCHK(hipMemcpyAsync(s, c->d_stat, sizeof(s), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    ms_total += ms;
-    st.kernel_launches += k;
-    st.group_steps += s[0];
-    st.lane_retired += s[1];
-    print_stamps(s);
-    if (s[2] == 0 || done >= max_steps) break;
-  }
-  if (to_end) regroup_observe_timed(c, used_timed, ms_total, st.lane_retired);
+    if (int rc = queue_launches(c, Q, first, count, chunk, max_steps, group, regroup != 0, done, k)) return rc;
+    if (int rc = collect_stats(c, k, st, running)) return rc;
+  } while (running && done < max_steps);
+  if (to_end) regroup_observe_timed(c, used_timed, st.kernel_ms, st.lane_retired);
   else regroup_observe(c, st.group_steps, st.lane_retired);
-  st.kernel_ms = ms_total;
   if (stats) *stats = st;
   return WTFGPU_OK;
 }
@@ -1323,44 +1337,32 @@ int wtfgpu_run_async(wtfgpu_ctx *c, uint32_t first, uint32_t count, uint64_t max
   if (!lanes_ok(c, first, count) || (first % c->P.lpw) || max_steps == 0 || max_steps > (1ull << 32))
     return WTFGPU_ERR_INVALID;
   if (!c->P.pool) return WTFGPU_ERR_STATE;
-  if (c->async_launches) return WTFGPU_ERR_STATE;
+  if (c->q->async_launches) return WTFGPU_ERR_STATE;
   HIPCHK(hipSetDevice(c->device));
   const u64 regroup = regroup_now(c, count);
   const u64 chunk = regroup ? regroup : max_steps;
   if (regroup)
     if (int rc = regroup_buffers(c)) return rc;
   const Dev Q = run_params(c, regroup != 0);
-  HIPCHK(hipEventRecord(c->ev_pre, c->stream));  // the plumbing before this run (wtfgpu_select_queue)
-  c->pre_valid = true;
-  HIPCHK(hipMemsetAsync(c->d_stat, 0, STAT_N * 8, c->stream));
-  HIPCHK(hipEventRecord(c->ev0, c->stream));
-  u32 k = 0;
-  for (u64 done = 0; done < max_steps; done += chunk, k++) {
-    if (int rc = launch_chunk(c, Q, first, count, std::min<u64>(chunk, max_steps - done), regroup != 0)) return rc;
-  }
-  HIPCHK(hipEventRecord(c->ev1, c->stream));
-  c->async_launches = k;
+  HIPCHK(hipEventRecord(c->q->ev_pre, c->q->stream));  // the plumbing before this run (wtfgpu_select_queue)
+  c->q->pre_valid = true;
+  u64 done = 0;
+  u32 k = 0;  // every launch of the run in one group: wtfgpu_run_wait reads the statistics
+  if (int rc = queue_launches(c, Q, first, count, chunk, max_steps, ~0ull, regroup != 0, done, k)) return rc;
+  c->q->async_launches = k;
   return WTFGPU_OK;
 }
 
 int wtfgpu_run_wait(wtfgpu_ctx *c, wtfgpu_run_stats_t *stats) {
   if (!c) return WTFGPU_ERR_INVALID;
   wtfgpu_run_stats_t st{};
-  if (c->async_launches) {
+  if (c->q->async_launches) {
     HIPCHK(hipSetDevice(c->device));
-    u64 s[STAT_N];
-    HIPCHK(hipMemcpyAsync(s, c->d_stat, sizeof(s), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    ring_reset(c);
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    st.kernel_launches = c->async_launches;
-    st.group_steps = s[0];
-    st.lane_retired = s[1];
-    st.kernel_ms = ms;
-    c->async_launches = 0;
+    u64 running = 0;
+    if (int rc = collect_stats(c, c->q->async_launches, st, running)) return rc;
+    ring_reset(c);  // the stream is idle
+    c->q->async_launches = 0;
     regroup_observe(c, st.group_steps, st.lane_retired);
-    print_stamps(s);
   }
   if (stats) *stats = st;
   return WTFGPU_OK;
@@ -1371,22 +1373,22 @@ int wtfgpu_prefetch_results(wtfgpu_ctx *c, uint32_t first, uint32_t count, wtfgp
   if (!lanes_ok(c, first, count) || !exits) return WTFGPU_ERR_INVALID;
   if (count == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  if (c->exq_cap < count) {  // stream-ordered, as ensure_scratch
-    if (c->d_exq) HIPCHK(hipFreeAsync(c->d_exq, c->stream));
-    c->d_exq = nullptr;
-    c->exq_cap = 0;
-    if (hipMallocAsync((void **)&c->d_exq, (u64)count * sizeof(wtfgpu_exit_t), c->stream) != hipSuccess)
+  if (c->q->exq_cap < count) {  // stream-ordered, as ensure_scratch
+    if (c->q->d_exq) HIPCHK(hipFreeAsync(c->q->d_exq, c->q->stream));
+    c->q->d_exq = nullptr;
+    c->q->exq_cap = 0;
+    if (hipMallocAsync((void **)&c->q->d_exq, (u64)count * sizeof(wtfgpu_exit_t), c->q->stream) != hipSuccess)
       return WTFGPU_ERR_OOM;
-    c->exq_cap = count;
+    c->q->exq_cap = count;
   }
-  k_pack_exits<<<(count + 255) / 256, 256, 0, c->stream>>>(c->P, first, count, c->d_exq);
+  k_pack_exits<<<(count + 255) / 256, 256, 0, c->q->stream>>>(c->P, first, count, c->q->d_exq);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(exits, c->d_exq, (u64)count * sizeof(wtfgpu_exit_t), hipMemcpyDeviceToHost, c->stream));
-  if (bytes) HIPCHK(hipMemcpyAsync(bytes, c->d_nbytes + first, (u64)count * 8, hipMemcpyDeviceToHost, c->stream));
-  if (dirty) HIPCHK(hipMemcpyAsync(dirty, c->d_ovcount + first, (u64)count * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(exits, c->q->d_exq, (u64)count * sizeof(wtfgpu_exit_t), hipMemcpyDeviceToHost, c->q->stream));
+  if (bytes) HIPCHK(hipMemcpyAsync(bytes, c->d_nbytes + first, (u64)count * 8, hipMemcpyDeviceToHost, c->q->stream));
+  if (dirty) HIPCHK(hipMemcpyAsync(dirty, c->d_ovcount + first, (u64)count * 4, hipMemcpyDeviceToHost, c->q->stream));
   if (stop_args && c->d_stopargs)
     HIPCHK(hipMemcpyAsync(stop_args, c->d_stopargs + (u64)first * 6, (u64)count * 48, hipMemcpyDeviceToHost,
-                          c->stream));
+                          c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -1400,99 +1402,85 @@ int wtfgpu_prefetch_coverage(wtfgpu_ctx *c, uint32_t first, uint32_t count, uint
     return WTFGPU_ERR_STATE;  // nothing to prefetch: the caller reads the sets itself
   }
   HIPCHK(hipSetDevice(c->device));
-  if (!c->d_pcov && hipMallocAsync((void **)&c->d_pcov, kPcovRips + kPcovCap * 8, c->stream) != hipSuccess) {
-    c->d_pcov = nullptr;
+  if (!c->q->d_pcov && hipMallocAsync((void **)&c->q->d_pcov, kPcovRips + kPcovCap * 8, c->q->stream) != hipSuccess) {
+    c->q->d_pcov = nullptr;
     return WTFGPU_ERR_OOM;
   }
-  HIPCHK(hipMemsetAsync(c->d_pcov, 0, 16, c->stream));
-  k_cov_collect_stopped<<<(count + 3) / 4, 256, 0, c->stream>>>(
-      c->P, first, count, (u32 *)(c->d_pcov + kPcovLanes), (u64 *)(c->d_pcov + kPcovRips), kPcovCap,
-      (unsigned long long *)c->d_pcov, (u32 *)(c->d_pcov + 8));
+  HIPCHK(hipMemsetAsync(c->q->d_pcov, 0, 16, c->q->stream));
+  k_cov_collect_stopped<<<(count + 3) / 4, 256, 0, c->q->stream>>>(
+      c->P, first, count, (u32 *)(c->q->d_pcov + kPcovLanes), (u64 *)(c->q->d_pcov + kPcovRips), kPcovCap,
+      (unsigned long long *)c->q->d_pcov, (u32 *)(c->q->d_pcov + 8));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(hdr, c->d_pcov, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hdr, c->q->d_pcov, 16, hipMemcpyDeviceToHost, c->q->stream));
   return WTFGPU_OK;
 }
 
 int wtfgpu_prefetched_coverage(wtfgpu_ctx *c, uint32_t *out_lanes, uint64_t *out_rips, uint64_t n) {
-  if (!c || (n && (!out_lanes || !out_rips)) || n > kPcovCap || (n && !c->d_pcov)) return WTFGPU_ERR_INVALID;
+  if (!c || (n && (!out_lanes || !out_rips)) || n > kPcovCap || (n && !c->q->d_pcov)) return WTFGPU_ERR_INVALID;
   if (n == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(out_lanes, c->d_pcov + kPcovLanes, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(out_rips, c->d_pcov + kPcovRips, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(out_lanes, c->q->d_pcov + kPcovLanes, n * 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipMemcpyAsync(out_rips, c->q->d_pcov + kPcovRips, n * 8, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
 int wtfgpu_clear_coverage_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n) {
   if (!c || (n && !lanes)) return WTFGPU_ERR_INVALID;
-  if (!c->d_covrip || n == 0) return WTFGPU_OK;
-  for (u32 i = 0; i < n; i++)
-    if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
+  if (!c->d_covrip || n == 0) return WTFGPU_OK;  // (without coverage sets a lane out of range passes: kept)
+  if (!lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  const u8 *st = ring_put(c, lanes, (u64)n * 4);
-  if (!st || ensure_scratch(c, (u64)n * 4)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, st, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  k_cov_clear<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, n);
+  if (int rc = stage_lanes(c, Upload::Ring, lanes, n)) return rc;
+  k_cov_clear<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, (const u32 *)c->q->d_scratch, n);
   HIPCHK(hipGetLastError());
   return WTFGPU_OK;
 }
 
 int wtfgpu_lane_seeds(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint64_t *seeds, int write) {
-  if (!c || (n && (!lanes || !seeds)) || !c->d_rdseed) return WTFGPU_ERR_INVALID;
+  if (!c || (n && (!lanes || !seeds)) || !c->d_rdseed || !lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;
   if (n == 0) return WTFGPU_OK;
-  for (u32 i = 0; i < n; i++)
-    if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  const u64 o_s = ((u64)n * 4 + 255) & ~255ull;
-  if (ensure_scratch(c, o_s + (u64)n * 8)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  if (write) HIPCHK(hipMemcpyAsync(c->d_scratch + o_s, seeds, (u64)n * 8, hipMemcpyHostToDevice, c->stream));
-  k_lane_seeds<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, n, (u64 *)(c->d_scratch + o_s),
-                                                       write);
+  Side s = side_in(write ? seeds : nullptr, (u64)n * 8);
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, &s, 1)) return rc;
+  k_lane_seeds<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, (const u32 *)c->q->d_scratch, n,
+                                                          (u64 *)(c->q->d_scratch + s.off), write);
   HIPCHK(hipGetLastError());
-  if (!write) HIPCHK(hipMemcpyAsync(seeds, c->d_scratch + o_s, (u64)n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (!write) return read_back(c, seeds, s);
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
 int wtfgpu_read_stop_args(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint64_t *out6) {
-  if (!c || (n && (!lanes || !out6)) || !c->d_stopargs) return WTFGPU_ERR_INVALID;
+  if (!c || (n && (!lanes || !out6)) || !c->d_stopargs || !lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;
   if (n == 0) return WTFGPU_OK;
-  for (u32 i = 0; i < n; i++)
-    if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  const u64 o_s = ((u64)n * 4 + 255) & ~255ull;
-  if (ensure_scratch(c, o_s + (u64)n * 48)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  k_stop_args<<<(n * 6 + 255) / 256, 256, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, n,
-                                                        (u64 *)(c->d_scratch + o_s));
+  Side out = side_room((u64)n * 48);
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, &out, 1)) return rc;
+  k_stop_args<<<(n * 6 + 255) / 256, 256, 0, c->q->stream>>>(c->P, (const u32 *)c->q->d_scratch, n,
+                                                             (u64 *)(c->q->d_scratch + out.off));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out6, c->d_scratch + o_s, (u64)n * 48, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return WTFGPU_OK;
+  return read_back(c, out6, out);
 }
 
 int wtfgpu_select_queue(wtfgpu_ctx *c, uint32_t queue) {
   if (!c || queue >= 2) return WTFGPU_ERR_INVALID;
-  if (queue == c->cur_queue) return WTFGPU_OK;
+  QueueRes &cur = *c->q, &next = c->queues[queue];
+  if (&next == &cur) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  QueueRes &next = c->queues[queue];
   if (!next.stream)
-    if (int rc = queue_create(next)) return rc;
+    if (int rc = queue_create(next, queue)) return rc;
   // The plumbing queued on the old queue without a wait (restores, status
   // and feed uploads, wtfgpu_restore_lanes ...) may touch lanes the new
   // queue runs: the new queue's later work is ordered after it. Only after
   // the plumbing: with a run in flight, after the event wtfgpu_run_async
   // recorded before its launches (the two queues' slices still overlap);
   // without one, after everything the old queue holds.
-  if (!c->async_launches) {
-    HIPCHK(hipEventRecord(c->ev_pre, c->stream));
-    c->pre_valid = true;
+  if (!cur.async_launches) {
+    HIPCHK(hipEventRecord(cur.ev_pre, cur.stream));
+    cur.pre_valid = true;
   }
-  if (c->pre_valid) HIPCHK(hipStreamWaitEvent(next.stream, c->ev_pre, 0));
-  queue_save(c, c->queues[c->cur_queue]);
-  queue_load(c, next);
-  c->cur_queue = queue;
+  if (cur.pre_valid) HIPCHK(hipStreamWaitEvent(next.stream, cur.ev_pre, 0));
+  c->q = &next;
   return WTFGPU_OK;
 }
 
@@ -1501,14 +1489,14 @@ static int lane_mem(wtfgpu_ctx *c, uint32_t lane, u32 op, u64 addr, void *buf, u
   if (!c || lane >= c->P.nlanes) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
   if (ensure_scratch(c, len + 64)) return WTFGPU_ERR_OOM;
-  i64 *d_res = (i64 *)c->d_scratch;
-  u8 *d_buf = c->d_scratch + 64;
-  if ((op == 2 || op == 4) && len) HIPCHK(hipMemcpyAsync(d_buf, buf, len, hipMemcpyHostToDevice, c->stream));
-  k_lane_mem<<<1, 64, 0, c->stream>>>(c->P, lane, op, addr, len, d_buf, d_res);
+  i64 *d_res = (i64 *)c->q->d_scratch;
+  u8 *d_buf = c->q->d_scratch + 64;
+  if ((op == 2 || op == 4) && len) HIPCHK(hipMemcpyAsync(d_buf, buf, len, hipMemcpyHostToDevice, c->q->stream));
+  k_lane_mem<<<1, 64, 0, c->q->stream>>>(c->P, lane, op, addr, len, d_buf, d_res);
   HIPCHK(hipGetLastError());
-  if ((op == 1 || op == 3) && len) HIPCHK(hipMemcpyAsync(buf, d_buf, len, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(result, d_res, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((op == 1 || op == 3) && len) HIPCHK(hipMemcpyAsync(buf, d_buf, len, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipMemcpyAsync(result, d_res, 8, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -1568,16 +1556,16 @@ static int apply_writes(wtfgpu_ctx *c, const wtfgpu_write_t *writes, uint32_t n,
   const u64 o_starts = (b_recs + 255) & ~255ull, o_st = (o_starts + b_starts + 255) & ~255ull,
             o_data = (o_st + b_st + 255) & ~255ull;
   if (ensure_scratch(c, o_data + data_len)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, recs.data(), b_recs, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_scratch + o_starts, starts.data(), b_starts, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_scratch + o_data, data, data_len, hipMemcpyHostToDevice, c->stream));
-  k_apply_writes<<<nl, 64, 0, c->stream>>>(c->P, (const WriteRec *)c->d_scratch,
-                                                       (const u32 *)(c->d_scratch + o_starts), nl,
-                                                       c->d_scratch + o_data, (i32 *)(c->d_scratch + o_st), phys);
+  HIPCHK(hipMemcpyAsync(c->q->d_scratch, recs.data(), b_recs, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemcpyAsync(c->q->d_scratch + o_starts, starts.data(), b_starts, hipMemcpyHostToDevice, c->q->stream));
+  HIPCHK(hipMemcpyAsync(c->q->d_scratch + o_data, data, data_len, hipMemcpyHostToDevice, c->q->stream));
+  k_apply_writes<<<nl, 64, 0, c->q->stream>>>(c->P, (const WriteRec *)c->q->d_scratch,
+                                                       (const u32 *)(c->q->d_scratch + o_starts), nl,
+                                                       c->q->d_scratch + o_data, (i32 *)(c->q->d_scratch + o_st), phys);
   HIPCHK(hipGetLastError());
   std::vector<i32> st(n);
-  HIPCHK(hipMemcpyAsync(st.data(), c->d_scratch + o_st, b_st, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(st.data(), c->q->d_scratch + o_st, b_st, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   int rc = WTFGPU_OK;
   for (u32 i = 0; i < n; i++) {
     if (status_out) status_out[order[i]] = st[i];
@@ -1595,40 +1583,28 @@ int wtfgpu_apply_phys_writes(wtfgpu_ctx *c, const wtfgpu_write_t *writes, uint32
   return apply_writes(c, writes, n, data, data_len, status_out, 1);
 }
 
-static int check_lane_list(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n) {
-  if (!c || !c->d_gpr || (n && !lanes)) return WTFGPU_ERR_INVALID;
-  for (uint32_t i = 0; i < n; i++)
-    if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
-  return WTFGPU_OK;
-}
-
 int wtfgpu_read_gprs_list(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint64_t *out18) {
   if (int rc = check_lane_list(c, lanes, n)) return rc;
   if (n == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  const u64 o_out = ((u64)n * 4 + 255) & ~255ull;
-  if (ensure_scratch(c, o_out + (u64)n * 18 * 8)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  k_gather_gprs<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, n,
-                                                         (u64 *)(c->d_scratch + o_out));
+  Side out = side_room((u64)n * 18 * 8);
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, &out, 1)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_gather_gprs<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, (const u32 *)S, n, (u64 *)(S + out.off));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out18, c->d_scratch + o_out, (u64)n * 18 * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return WTFGPU_OK;
+  return read_back(c, out18, out);
 }
 
 int wtfgpu_write_gprs_list(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, const uint64_t *in18) {
   if (int rc = check_lane_list(c, lanes, n)) return rc;
   if (n == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  const u64 o_in = ((u64)n * 4 + 255) & ~255ull;
-  if (ensure_scratch(c, o_in + (u64)n * 18 * 8)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_scratch + o_in, in18, (u64)n * 18 * 8, hipMemcpyHostToDevice, c->stream));
-  k_scatter_gprs<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, n,
-                                                          (const u64 *)(c->d_scratch + o_in));
+  Side in = side_in(in18, (u64)n * 18 * 8);
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, &in, 1)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_scatter_gprs<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, (const u32 *)S, n, (const u64 *)(S + in.off));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -1636,16 +1612,12 @@ int wtfgpu_read_dirty_list(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uin
   if (int rc = check_lane_list(c, lanes, n)) return rc;
   if (n == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  const u64 stride = (u64)c->P.K + 1;
-  const u64 o_out = ((u64)n * 4 + 255) & ~255ull;
-  if (ensure_scratch(c, o_out + (u64)n * stride * 4)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  k_gather_dirty<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, n,
-                                                          (u32 *)(c->d_scratch + o_out));
+  Side o = side_room((u64)n * ((u64)c->P.K + 1) * 4);
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, &o, 1)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_gather_dirty<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, (const u32 *)S, n, (u32 *)(S + o.off));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, c->d_scratch + o_out, (u64)n * stride * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return WTFGPU_OK;
+  return read_back(c, out, o);
 }
 
 uint32_t wtfgpu_overlay_pages(wtfgpu_ctx *c) { return c ? c->P.K : 0; }
@@ -1655,16 +1627,12 @@ int wtfgpu_gather_pages(wtfgpu_ctx *c, const uint32_t *lanes, const uint64_t *gp
   if (n == 0) return WTFGPU_OK;
   if (!gpas || !out || !c->P.pool) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  const u64 o_gpa = ((u64)n * 4 + 255) & ~255ull, o_out = (o_gpa + (u64)n * 8 + 4095) & ~4095ull;
-  if (ensure_scratch(c, o_out + (u64)n * WTFGPU_PAGE_SIZE)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_scratch + o_gpa, gpas, (u64)n * 8, hipMemcpyHostToDevice, c->stream));
-  k_gather_pages<<<n, 256, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, (const u64 *)(c->d_scratch + o_gpa), n,
-                                           c->d_scratch + o_out);
+  Side s[] = {side_in(gpas, (u64)n * 8), side_room((u64)n * WTFGPU_PAGE_SIZE, 4096)};
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, s, 2)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_gather_pages<<<n, 256, 0, c->q->stream>>>(c->P, (const u32 *)S, (const u64 *)(S + s[0].off), n, S + s[1].off);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, c->d_scratch + o_out, (u64)n * WTFGPU_PAGE_SIZE, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return WTFGPU_OK;
+  return read_back(c, out, s[1]);
 }
 
 int wtfgpu_inject_fault(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32_t vector, uint32_t error,
@@ -1673,17 +1641,13 @@ int wtfgpu_inject_fault(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32
   if (n == 0) return WTFGPU_OK;
   if (!addrs || !delivered || vector > 31) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  const u64 o_a = ((u64)n * 4 + 255) & ~255ull, o_ok = (o_a + (u64)n * 8 + 255) & ~255ull;
-  if (ensure_scratch(c, o_ok + (u64)n * 4)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_scratch + o_a, addrs, (u64)n * 8, hipMemcpyHostToDevice, c->stream));
-  k_inject_fault<<<(n + 63) / 64, 64, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch,
-                                                     (const u64 *)(c->d_scratch + o_a), n, vector, error,
-                                                     (i32 *)(c->d_scratch + o_ok));
+  Side s[] = {side_in(addrs, (u64)n * 8), side_room((u64)n * 4)};
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, s, 2)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_inject_fault<<<(n + 63) / 64, 64, 0, c->q->stream>>>(c->P, (const u32 *)S, (const u64 *)(S + s[0].off), n, vector,
+                                                         error, (i32 *)(S + s[1].off));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(delivered, c->d_scratch + o_ok, (u64)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return WTFGPU_OK;
+  return read_back(c, delivered, s[1]);
 }
 
 int wtfgpu_gather_bytes(wtfgpu_ctx *c, const uint32_t *lanes, const uint64_t *gpas, uint32_t n, uint32_t len,
@@ -1694,16 +1658,12 @@ int wtfgpu_gather_bytes(wtfgpu_ctx *c, const uint32_t *lanes, const uint64_t *gp
   for (u32 i = 0; i < n; i++)
     if ((gpas[i] & 0xfff) + len > WTFGPU_PAGE_SIZE) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  const u64 o_gpa = ((u64)n * 4 + 255) & ~255ull, o_out = (o_gpa + (u64)n * 8 + 255) & ~255ull;
-  if (ensure_scratch(c, o_out + (u64)n * len)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_scratch + o_gpa, gpas, (u64)n * 8, hipMemcpyHostToDevice, c->stream));
-  k_gather_bytes<<<n, 64, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, (const u64 *)(c->d_scratch + o_gpa), n,
-                                          len, c->d_scratch + o_out);
+  Side s[] = {side_in(gpas, (u64)n * 8), side_room((u64)n * len)};
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, s, 2)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_gather_bytes<<<n, 64, 0, c->q->stream>>>(c->P, (const u32 *)S, (const u64 *)(S + s[0].off), n, len, S + s[1].off);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, c->d_scratch + o_out, (u64)n * len, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return WTFGPU_OK;
+  return read_back(c, out, s[1]);
 }
 
 static int lane_cr_ptr(wtfgpu_ctx *c, uint32_t lane, uint32_t cr, u8 **p) {
@@ -1716,8 +1676,8 @@ int wtfgpu_lane_get_cr(wtfgpu_ctx *c, uint32_t lane, uint32_t cr, uint64_t *valu
   u8 *p = nullptr;
   if (!value || lane_cr_ptr(c, lane, cr, &p)) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(value, p, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(value, p, 8, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -1725,9 +1685,9 @@ int wtfgpu_lane_set_cr(wtfgpu_ctx *c, uint32_t lane, uint32_t cr, uint64_t value
   u8 *p = nullptr;
   if (lane_cr_ptr(c, lane, cr, &p)) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(p, &value, 8, hipMemcpyHostToDevice, c->stream));
-  if (cr == 3) HIPCHK(hipMemsetAsync(c->d_tlbok + lane, 0, 4, c->stream));  // translations of the old cr3
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(p, &value, 8, hipMemcpyHostToDevice, c->q->stream));
+  if (cr == 3) HIPCHK(hipMemsetAsync(c->d_tlbok + lane, 0, 4, c->q->stream));  // translations of the old cr3
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -1750,13 +1710,13 @@ int wtfgpu_read_dirty(wtfgpu_ctx *c, uint32_t lane, uint64_t *gpas, uint32_t cap
   if (!c || lane >= c->P.nlanes || !n) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
   u32 cnt = 0;  // (on the queue's stream: after its queued restores)
-  HIPCHK(hipMemcpyAsync(&cnt, c->d_ovcount + lane, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(&cnt, c->d_ovcount + lane, 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   *n = cnt;
   for (u32 k = 0; k < cnt && k < cap; k++) {
     u32 g = 0;
-    HIPCHK(hipMemcpyAsync(&g, c->d_ovgpfn + (u64)k * c->P.nlanes + lane, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(&g, c->d_ovgpfn + (u64)k * c->P.nlanes + lane, 4, hipMemcpyDeviceToHost, c->q->stream));
+    HIPCHK(hipStreamSynchronize(c->q->stream));
     gpas[k] = (u64)g << 12;
   }
   return WTFGPU_OK;
@@ -1768,26 +1728,26 @@ static int collect_sets(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t first, ui
                         uint64_t *out_rips, uint64_t cap, uint64_t *total, uint32_t *overflow, int clear) {
   HIPCHK(hipSetDevice(c->device));
   const u64 room = std::max<u64>(cap, 1);
-  const u64 o_n = ((u64)(lanes ? n : 0) * 4 + 255) & ~255ull, o_l = o_n + 256, o_r = (o_l + room * 4 + 255) & ~255ull;
-  if (ensure_scratch(c, o_r + room * 8)) return WTFGPU_ERR_OOM;
-  if (lanes) HIPCHK(hipMemcpyAsync(c->d_scratch, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_scratch + o_n, 0, 16, c->stream));
-  k_cov_collect<<<n, 256, 0, c->stream>>>(c->P, lanes ? (const u32 *)c->d_scratch : nullptr, first, n,
-                                          (u32 *)(c->d_scratch + o_l), (u64 *)(c->d_scratch + o_r), cap,
-                                          (unsigned long long *)(c->d_scratch + o_n), (u32 *)(c->d_scratch + o_n + 8));
+  // header (total, overflow) | lanes out | rips out
+  Side s[] = {side_room(256), side_room(room * 4), side_room(room * 8)};
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, s, 3)) return rc;
+  u8 *const S = c->q->d_scratch, *const H = S + s[0].off;
+  HIPCHK(hipMemsetAsync(H, 0, 16, c->q->stream));
+  k_cov_collect<<<n, 256, 0, c->q->stream>>>(c->P, lanes ? (const u32 *)S : nullptr, first, n, (u32 *)(S + s[1].off),
+                                             (u64 *)(S + s[2].off), cap, (unsigned long long *)H, (u32 *)(H + 8));
   HIPCHK(hipGetLastError());
   u64 hdr[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(hdr, c->d_scratch + o_n, 16, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(hdr, H, 16, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   if (clear && lanes && hdr[0] <= cap) {  // everything was read: the sets empty (ordered before later work)
-    k_cov_clear<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, (const u32 *)c->d_scratch, n);
+    k_cov_clear<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, (const u32 *)S, n);
     HIPCHK(hipGetLastError());
   }
   const u64 m = std::min(hdr[0], cap);
   if (m) {
-    HIPCHK(hipMemcpyAsync(out_lanes, c->d_scratch + o_l, m * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out_rips, c->d_scratch + o_r, m * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(out_lanes, S + s[1].off, m * 4, hipMemcpyDeviceToHost, c->q->stream));
+    HIPCHK(hipMemcpyAsync(out_rips, S + s[2].off, m * 8, hipMemcpyDeviceToHost, c->q->stream));
+    HIPCHK(hipStreamSynchronize(c->q->stream));
   }
   if (overflow) *overflow = (u32)hdr[1] & 1;
   *total = hdr[0];
@@ -1808,9 +1768,10 @@ int wtfgpu_collect_coverage_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t
   if (!c || !total || (n && !lanes) || (cap && (!out_lanes || !out_rips))) return WTFGPU_ERR_INVALID;
   *total = 0;
   if (overflow) *overflow = 0;
+  // the range check comes after the look for the sets here and before it in
+  // wtfgpu_attribute_coverage: an accident, kept (callers see the return codes)
   if (!c->d_covrip || n == 0) return WTFGPU_OK;
-  for (u32 i = 0; i < n; i++)
-    if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
+  if (!lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;
   return collect_sets(c, lanes, 0, n, out_lanes, out_rips, cap, total, overflow, 1);
 }
 
@@ -1826,43 +1787,40 @@ int wtfgpu_attribute_coverage(wtfgpu_ctx *c, const uint32_t *lanes, const uint8_
   *total = 0;
   if (entries) *entries = 0;
   if (overflow) *overflow = 0;
-  for (u32 i = 0; i < n; i++)
-    if (lanes[i] >= c->P.nlanes) return WTFGPU_ERR_INVALID;
+  if (!lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;  // (before the look for the sets: see above)
   if (!c->d_covrip || n == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   const u32 all = flags & WTFGPU_ATTRIB_ALL ? 1 : 0;
   const auto up = [](u64 v) { return (v + 255) & ~255ull; };
-  // queue scratch: lanes | revoke | cnt[n + 1] | off[n + 1] | header (entries, overflow) | scan scratch
   size_t tmp_n = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_n, (u32 *)nullptr, (u32 *)nullptr, (int)(n + 1), c->stream));
-  const u64 o_rev = up((u64)n * 4), o_cnt = o_rev + up(n), o_off = o_cnt + up((u64)(n + 1) * 4),
-            o_hdr = o_off + up((u64)(n + 1) * 4), o_tmp = o_hdr + 256;
-  if (ensure_scratch(c, o_tmp + tmp_n)) return WTFGPU_ERR_OOM;
-  u8 *const S = c->d_scratch;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_n, (u32 *)nullptr, (u32 *)nullptr, (int)(n + 1), c->q->stream));
+  // queue scratch: lanes | revoke | cnt[n + 1] | off[n + 1] | header (entries, overflow) | scan scratch
+  const bool rev = revoke && !all;
+  Side sc[] = {side_in(rev ? revoke : nullptr, n), side_room((u64)(n + 1) * 4), side_room((u64)(n + 1) * 4),
+               side_room(256), side_room(tmp_n)};
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, sc, 5)) return rc;
+  const u64 o_rev = sc[0].off, o_cnt = sc[1].off, o_off = sc[2].off, o_hdr = sc[3].off, o_tmp = sc[4].off;
+  u8 *const S = c->q->d_scratch;
   const u32 *d_lanes = (const u32 *)S;
   const u8 *d_rev = S + o_rev;
   u32 *d_cnt = (u32 *)(S + o_cnt), *d_off = (u32 *)(S + o_off);
-  HIPCHK(hipMemcpyAsync(S, lanes, (u64)n * 4, hipMemcpyHostToDevice, c->stream));
-  if (revoke && !all)
-    HIPCHK(hipMemcpyAsync(S + o_rev, revoke, n, hipMemcpyHostToDevice, c->stream));
-  else
-    HIPCHK(hipMemsetAsync(S + o_rev, 0, n, c->stream));
-  HIPCHK(hipMemsetAsync(S + o_cnt, 0, (u64)(n + 1) * 4, c->stream));
-  HIPCHK(hipMemsetAsync(S + o_hdr, 0, 16, c->stream));
+  if (!rev) HIPCHK(hipMemsetAsync(S + o_rev, 0, n, c->q->stream));
+  HIPCHK(hipMemsetAsync(S + o_cnt, 0, (u64)(n + 1) * 4, c->q->stream));
+  HIPCHK(hipMemsetAsync(S + o_hdr, 0, 16, c->q->stream));
   const u32 wblocks = (n + 3) / 4;
-  k_attr_scan<<<wblocks, 256, 0, c->stream>>>(c->P, d_lanes, n, all, d_cnt, nullptr, nullptr,
+  k_attr_scan<<<wblocks, 256, 0, c->q->stream>>>(c->P, d_lanes, n, all, d_cnt, nullptr, nullptr,
                                               (unsigned long long *)(S + o_hdr), (u32 *)(S + o_hdr + 8));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(S + o_tmp, tmp_n, d_cnt, d_off, (int)(n + 1), c->stream));
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(S + o_tmp, tmp_n, d_cnt, d_off, (int)(n + 1), c->q->stream));
   u64 hdr[2] = {0, 0};
   u32 s = 0;  // candidates (the scan's last sum; 32 bits hold nlanes * H of any context that fits the device)
-  HIPCHK(hipMemcpyAsync(hdr, S + o_hdr, 16, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(&s, d_off + n, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(hdr, S + o_hdr, 16, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipMemcpyAsync(&s, d_off + n, 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   if (entries) *entries = hdr[0];
   if (overflow) *overflow = (u32)hdr[1] & 1;
   const auto clear = [&]() -> int {  // everything was read: the sets empty (ordered before later work)
-    k_cov_clear<<<(n + 255) / 256, 256, 0, c->stream>>>(c->P, d_lanes, n);
+    k_cov_clear<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, d_lanes, n);
     HIPCHK(hipGetLastError());
     return WTFGPU_OK;
   };
@@ -1876,7 +1834,7 @@ int wtfgpu_attribute_coverage(wtfgpu_ctx *c, const uint32_t *lanes, const uint8_
   while (T < 2ull * s && T < (1u << 31)) T <<= 1;
   if (T < 2ull * s) return WTFGPU_ERR_OOM;
   size_t tmp_s = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_s, (u32 *)nullptr, (u32 *)nullptr, (int)(s + 1), c->stream));
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_s, (u32 *)nullptr, (u32 *)nullptr, (int)(s + 1), c->q->stream));
   const u64 a_vals = up((u64)s * 8), a_pos = a_vals + up((u64)s * 8), a_slot = a_pos + up((u64)s * 4),
             a_keys = a_slot + up((u64)s * 4), a_own = a_keys + up(((u64)T + 1) * 8),
             a_flag = a_own + up(((u64)T + 1) * 4), a_at = a_flag + up(((u64)s + 1) * 4),
@@ -1892,9 +1850,9 @@ int wtfgpu_attribute_coverage(wtfgpu_ctx *c, const uint32_t *lanes, const uint8_
   u8 *const A = c->d_attr;
   u64 *d_raw = (u64 *)A, *d_vals = (u64 *)(A + a_vals);
   u32 *d_pos = (u32 *)(A + a_pos);
-  k_attr_scan<<<wblocks, 256, 0, c->stream>>>(c->P, d_lanes, n, all, nullptr, d_off, d_raw, nullptr, nullptr);
+  k_attr_scan<<<wblocks, 256, 0, c->q->stream>>>(c->P, d_lanes, n, all, nullptr, d_off, d_raw, nullptr, nullptr);
   HIPCHK(hipGetLastError());
-  k_attr_sort<<<wblocks, 256, 0, c->stream>>>(d_cnt, d_off, n, d_raw, d_vals, d_pos);
+  k_attr_sort<<<wblocks, 256, 0, c->q->stream>>>(d_cnt, d_off, n, d_raw, d_vals, d_pos);
   HIPCHK(hipGetLastError());
   const u32 *d_rpos = d_pos;  // the result, on the device
   const u64 *d_rvals = d_vals;
@@ -1902,28 +1860,29 @@ int wtfgpu_attribute_coverage(wtfgpu_ctx *c, const uint32_t *lanes, const uint8_
   if (!all) {
     u32 *d_slot = (u32 *)(A + a_slot), *d_own = (u32 *)(A + a_own), *d_flag = (u32 *)(A + a_flag),
         *d_at = (u32 *)(A + a_at);
-    HIPCHK(hipMemsetAsync(A + a_keys, 0xff, a_flag - a_keys, c->stream));  // keys and own: all bits set
-    k_attr_owner<<<(s + 255) / 256, 256, 0, c->stream>>>(d_vals, d_pos, s, d_rev, (u64 *)(A + a_keys), d_own, T, d_slot);
+    HIPCHK(hipMemsetAsync(A + a_keys, 0xff, a_flag - a_keys, c->q->stream));  // keys and own: all bits set
+    k_attr_owner<<<(s + 255) / 256, 256, 0, c->q->stream>>>(d_vals, d_pos, s, d_rev, (u64 *)(A + a_keys), d_own, T,
+                                                            d_slot);
     HIPCHK(hipGetLastError());
-    k_attr_keep<<<s / 256 + 1, 256, 0, c->stream>>>(d_pos, d_slot, d_own, s, d_flag);
+    k_attr_keep<<<s / 256 + 1, 256, 0, c->q->stream>>>(d_pos, d_slot, d_own, s, d_flag);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(A + a_tmp, tmp_s, d_flag, d_at, (int)(s + 1), c->stream));
-    k_attr_emit<<<(s + 255) / 256, 256, 0, c->stream>>>(d_vals, d_pos, d_flag, d_at, s, (u32 *)(A + a_opos),
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(A + a_tmp, tmp_s, d_flag, d_at, (int)(s + 1), c->q->stream));
+    k_attr_emit<<<(s + 255) / 256, 256, 0, c->q->stream>>>(d_vals, d_pos, d_flag, d_at, s, (u32 *)(A + a_opos),
                                                         (u64 *)(A + a_oval));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&m, d_at + s, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(&m, d_at + s, 4, hipMemcpyDeviceToHost, c->q->stream));
+    HIPCHK(hipStreamSynchronize(c->q->stream));
     d_rpos = (const u32 *)(A + a_opos);
     d_rvals = (const u64 *)(A + a_oval);
   }
   *total = m;
   if (cap < m) return WTFGPU_OK;  // nothing emptied: the caller calls again with room
   if (m) {
-    HIPCHK(hipMemcpyAsync(out_pos, d_rpos, (u64)m * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out_vals, d_rvals, (u64)m * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out_pos, d_rpos, (u64)m * 4, hipMemcpyDeviceToHost, c->q->stream));
+    HIPCHK(hipMemcpyAsync(out_vals, d_rvals, (u64)m * 8, hipMemcpyDeviceToHost, c->q->stream));
   }
   const int rc = clear();
-  HIPCHK(hipStreamSynchronize(c->stream));  // d_attr serves both queues: idle at every return
+  HIPCHK(hipStreamSynchronize(c->q->stream));  // d_attr serves both queues: idle at every return
   return rc;
 }
 
@@ -1932,10 +1891,10 @@ int wtfgpu_commit_coverage(wtfgpu_ctx *c, const uint64_t *rips, uint64_t n) {
   if (n == 0 || !c->d_covmap) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   if (ensure_scratch(c, n * 8)) return WTFGPU_ERR_OOM;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, rips, n * 8, hipMemcpyHostToDevice, c->stream));
-  k_cov_commit<<<(u32)((n + 255) / 256), 256, 0, c->stream>>>(c->P, (const u64 *)c->d_scratch, n);
+  HIPCHK(hipMemcpyAsync(c->q->d_scratch, rips, n * 8, hipMemcpyHostToDevice, c->q->stream));
+  k_cov_commit<<<(u32)((n + 255) / 256), 256, 0, c->q->stream>>>(c->P, (const u64 *)c->q->d_scratch, n);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -1943,21 +1902,19 @@ int wtfgpu_reset_coverage(wtfgpu_ctx *c) {
   if (!c) return WTFGPU_ERR_INVALID;
   if (!c->d_covmap) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemsetAsync(c->d_covmap, 0, c->ncovslots * WTFGPU_PAGE_SIZE, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_covshadow, 0, c->ncovslots * WTFGPU_PAGE_SIZE, c->stream));
-  if (c->d_extra) HIPCHK(hipMemsetAsync(c->d_extra, 0xff, (u64)kExtraEntries * 8, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemsetAsync(c->d_covmap, 0, c->ncovslots * WTFGPU_PAGE_SIZE, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_covshadow, 0, c->ncovslots * WTFGPU_PAGE_SIZE, c->q->stream));
+  if (c->d_extra) HIPCHK(hipMemsetAsync(c->d_extra, 0xff, (u64)kExtraEntries * 8, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return guc_clear(c);  // shared entries and images carry UC_COVERED
 }
 
 int wtfgpu_set_trace(wtfgpu_ctx *c, uint32_t per_lane) {
   if (!c || !c->P.nlanes) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   dfree(c->d_trace);
   dfree(c->d_tracecnt);
-  c->d_trace = nullptr;
-  c->d_tracecnt = nullptr;
   c->P.trace = nullptr;
   c->P.trace_cnt = nullptr;
   c->P.trace_cap = 0;
@@ -1976,12 +1933,13 @@ int wtfgpu_read_trace(wtfgpu_ctx *c, uint32_t lane, uint64_t *rips, uint64_t cap
   if (!c || !n || (cap && !rips) || lane >= c->P.nlanes || !c->d_trace) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
   u32 cnt = 0;
-  HIPCHK(hipMemcpyAsync(&cnt, c->d_tracecnt + lane, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(&cnt, c->d_tracecnt + lane, 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   *n = cnt;
   const u64 k = std::min<u64>(std::min<u64>(cnt, c->P.trace_cap), cap);
-  if (k) HIPCHK(hipMemcpyAsync(rips, c->d_trace + (u64)lane * c->P.trace_cap, k * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (k)
+    HIPCHK(hipMemcpyAsync(rips, c->d_trace + (u64)lane * c->P.trace_cap, k * 8, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -1989,14 +1947,13 @@ int wtfgpu_read_trace(wtfgpu_ctx *c, uint32_t lane, uint64_t *rips, uint64_t cap
 int wtfgpu_set_tenet(wtfgpu_ctx *c, uint64_t bytes_per_lane) {
   if (!c || !c->d_gpr || (bytes_per_lane & 7)) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   dfree(c->d_tn_buf);
   dfree(c->d_tn_pos);
   dfree(c->d_tn_cpos);
   dfree(c->d_tn_ipos);
   dfree(c->d_tn_last);
   dfree(c->d_tn_mute);
-  c->d_tn_buf = nullptr, c->d_tn_pos = c->d_tn_cpos = c->d_tn_ipos = c->d_tn_last = nullptr, c->d_tn_mute = nullptr;
   TenetDev T{};
   c->tn_cap = 0;
   if (bytes_per_lane) {
@@ -2020,12 +1977,12 @@ int wtfgpu_read_tenet(wtfgpu_ctx *c, uint32_t lane, uint8_t *buf, uint64_t cap, 
   if (!c || !n || (cap && !buf) || lane >= c->P.nlanes || !c->d_tn_buf) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
   u64 pos = 0;
-  HIPCHK(hipMemcpyAsync(&pos, c->d_tn_pos + lane, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(&pos, c->d_tn_pos + lane, 8, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   *n = pos;
   const u64 k = std::min<u64>(std::min<u64>(pos, c->tn_cap), cap);
-  if (k) HIPCHK(hipMemcpyAsync(buf, c->d_tn_buf + (u64)lane * c->tn_cap, k, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (k) HIPCHK(hipMemcpyAsync(buf, c->d_tn_buf + (u64)lane * c->tn_cap, k, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -2048,20 +2005,20 @@ int wtfgpu_coverage_absorb(wtfgpu_ctx *c, uint64_t *rips, uint64_t cap, uint64_t
   HIPCHK(hipSetDevice(c->device));
   const u64 bytes = c->ncovslots * WTFGPU_PAGE_SIZE, n16 = bytes / 16;
   if (ensure_scratch(c, 256 + cap * 8)) return WTFGPU_ERR_OOM;
-  unsigned long long *d_count = (unsigned long long *)c->d_scratch;
-  u64 *d_idx = (u64 *)(c->d_scratch + 256);
-  HIPCHK(hipMemsetAsync(d_count, 0, 8, c->stream));
-  k_cov_absorb<<<(u32)((n16 + 255) / 256), 256, 0, c->stream>>>(c->d_covmap, c->d_covshadow, n16, d_idx, cap, d_count,
-                                                                 cap ? 1 : 0);
+  unsigned long long *d_count = (unsigned long long *)c->q->d_scratch;
+  u64 *d_idx = (u64 *)(c->q->d_scratch + 256);
+  HIPCHK(hipMemsetAsync(d_count, 0, 8, c->q->stream));
+  k_cov_absorb<<<(u32)((n16 + 255) / 256), 256, 0, c->q->stream>>>(c->d_covmap, c->d_covshadow, n16, d_idx, cap,
+                                                                   d_count, cap ? 1 : 0);
   HIPCHK(hipGetLastError());
   u64 total = 0;
-  HIPCHK(hipMemcpyAsync(&total, d_count, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(&total, d_count, 8, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   const u64 m = std::min(total, cap);
   if (m) {
     std::vector<u64> idx(m);
-    HIPCHK(hipMemcpyAsync(idx.data(), d_idx, m * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(idx.data(), d_idx, m * 8, hipMemcpyDeviceToHost, c->q->stream));
+    HIPCHK(hipStreamSynchronize(c->q->stream));
     std::sort(idx.begin(), idx.end());
     for (u64 i = 0; i < m; i++) rips[i] = (c->code_vpns[idx[i] / WTFGPU_PAGE_SIZE] << 12) | (idx[i] % WTFGPU_PAGE_SIZE);
   }
@@ -2075,9 +2032,9 @@ int wtfgpu_coverage_merge_in(wtfgpu_ctx *c, const void *dev_src, uint64_t bytes)
   const u64 mb = c->ncovslots * WTFGPU_PAGE_SIZE, n16 = mb / 16;
   if (bytes != mb) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  k_cov_merge_in<<<(u32)((n16 + 255) / 256), 256, 0, c->stream>>>((uint4 *)c->d_covmap, (const uint4 *)dev_src, n16);
+  k_cov_merge_in<<<(u32)((n16 + 255) / 256), 256, 0, c->q->stream>>>((uint4 *)c->d_covmap, (const uint4 *)dev_src, n16);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -2094,8 +2051,8 @@ int wtfgpu_coverage_rips(wtfgpu_ctx *c, uint64_t *rips, uint64_t cap, uint64_t *
   if (!c->d_covmap) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   std::vector<u8> m(c->ncovslots * WTFGPU_PAGE_SIZE);
-  HIPCHK(hipMemcpyAsync(m.data(), c->d_covmap, m.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(m.data(), c->d_covmap, m.size(), hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   u64 k = 0;
   for (u64 s = 0; s < c->ncovslots; s++)
     for (u64 o = 0; o < WTFGPU_PAGE_SIZE; o++)
@@ -2110,8 +2067,8 @@ int wtfgpu_coverage_rips(wtfgpu_ctx *c, uint64_t *rips, uint64_t cap, uint64_t *
 int wtfgpu_read_bytes(wtfgpu_ctx *c, uint32_t first, uint32_t count, uint64_t *out) {
   if (!lanes_ok(c, first, count) || !out) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(out, c->d_nbytes + first, (u64)count * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->d_nbytes + first, (u64)count * 8, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
@@ -2122,16 +2079,16 @@ int wtfgpu_read_edge_counts(wtfgpu_ctx *c, uint32_t first, uint32_t count, uint3
     return WTFGPU_OK;
   }
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(out2, c->d_edgecnt + 2ull * first, 8ull * count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(out2, c->d_edgecnt + 2ull * first, 8ull * count, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 
 int wtfgpu_read_dirty_counts(wtfgpu_ctx *c, uint32_t first, uint32_t count, uint32_t *out) {
   if (!lanes_ok(c, first, count) || !out) return WTFGPU_ERR_INVALID;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(out, c->d_ovcount + first, (u64)count * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->d_ovcount + first, (u64)count * 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 

@@ -114,6 +114,10 @@ class Engine:
         _chk(self.L.wtfgpu_run_wait(self.ctx, C.byref(st)), "run_wait")
         return st
 
+    def select_queue(self, queue: int):
+        """Every later call is issued on queue 0 or 1 (wtfgpu_select_queue)."""
+        _chk(self.L.wtfgpu_select_queue(self.ctx, queue), "select_queue")
+
     def exits(self, first=0, count=None):
         count = self.nlanes - first if count is None else count
         arr = (abi.Exit * count)()
