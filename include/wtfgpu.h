@@ -68,7 +68,7 @@ enum wtfgpu_status {
   WTFGPU_EXIT_FAULT = 5,      /* architectural exception raised; vector/error/addr in exit */
   WTFGPU_EXIT_UNIMPLEMENTED = 6, /* opcode outside the engine's ISA subset */
   WTFGPU_EXIT_CR3 = 7,        /* cr3 write != initial cr3 (bochscpu_backend.cc:628-657) */
-  WTFGPU_EXIT_OVERLAY_FULL = 8, /* lane ran out of copy-on-write pages */
+  WTFGPU_EXIT_OVERLAY_FULL = 8, /* lane ran out of copy-on-write pages (with a spill pool: see wtfgpu_alloc_spill) */
   WTFGPU_EXIT_STOPPED = 9,    /* host called Stop(); result kept on the host */
   WTFGPU_EXIT_IDLE = 10,      /* lane holds no testcase */
   WTFGPU_EXIT_STOP_OK = 11,   /* a device action stopped the lane with Ok_t() (feed drained, STOP_OK) */
@@ -182,6 +182,38 @@ int wtfgpu_load_pool(wtfgpu_ctx *ctx, const uint64_t *gpfns, const uint8_t *page
 int wtfgpu_alloc_lanes(wtfgpu_ctx *ctx, uint32_t nlanes, uint32_t overlay_pages,
                        uint32_t cov_entries);
 uint32_t wtfgpu_lane_count(wtfgpu_ctx *ctx);
+
+/* Spill pool (no bochscpu counterpart: DirtyGpa takes any number of pages,
+ * bochscpu_backend.cc:887-889). Called after wtfgpu_alloc_lanes, before the
+ * lanes run: a lane whose overlay_pages private copy-on-write pages are full
+ * takes further ones from a device-wide pool of pool_pages pages, lane_max of
+ * them at most, so it may dirty overlay_pages + lane_max pages. Where a page
+ * lives changes nothing the guest or any read-back call sees. Without this
+ * call (or with 0, 0, which drops the pool) nothing spills.
+ * A lane still ends as WTFGPU_EXIT_OVERLAY_FULL in two cases:
+ *  - it holds overlay_pages + lane_max pages already: a property of the
+ *    testcase, the same on every run;
+ *  - the pool is empty at that moment: this depends on what the other lanes
+ *    hold just then and is NOT reproducible from a seed. Such failures are
+ *    counted apart (wtfgpu_spill_stats_t::pool_empty), so that a campaign can
+ *    check that it had none.
+ * Pages go back to the pool when their lane is restored. Replacing a pool
+ * that still has pages in use is WTFGPU_ERR_INVALID; wtfgpu_alloc_lanes drops
+ * the pool with the lanes. */
+int wtfgpu_alloc_spill(wtfgpu_ctx *ctx, uint64_t pool_pages, uint32_t lane_max);
+/* Dirty pages a lane can hold: overlay_pages + lane_max. */
+uint32_t wtfgpu_dirty_capacity(wtfgpu_ctx *ctx);
+typedef struct wtfgpu_spill_stats {
+  uint64_t pool_pages;     /* the pool's size (0: no pool, everything below 0) */
+  uint64_t lane_max;
+  uint64_t in_use;         /* pool pages owned now */
+  uint64_t peak;           /* most owned at one time */
+  uint64_t lanes_spilled;  /* times a lane took its first pool page */
+  uint64_t pool_empty;     /* allocations that failed because no page was free */
+  uint64_t claims;         /* pool pages handed out, ever */
+} wtfgpu_spill_stats_t;
+/* Counters since wtfgpu_alloc_spill, as of the selected queue's queued work. */
+int wtfgpu_spill_stats(wtfgpu_ctx *ctx, wtfgpu_spill_stats_t *out);
 
 int wtfgpu_set_initial_state(wtfgpu_ctx *ctx, const wtfgpu_regs_t *regs);
 int wtfgpu_set_limit(wtfgpu_ctx *ctx, uint64_t limit);
@@ -393,7 +425,8 @@ int wtfgpu_apply_phys_writes(wtfgpu_ctx *ctx, const wtfgpu_write_t *writes, uint
  * (the batched form of Get/SetReg and of the dirty-page and PhysTranslate views,
  * bochscpu_backend.cc:1124-1190, :887-900):
  * gprs + rip + rflags (18 u64 per lane) of a lane list, read / written;
- * dirty lists: out[i * (overlay_pages + 1)] = count, then the gpfns;
+ * dirty lists: out[i * (wtfgpu_dirty_capacity + 1)] = count, then the gpfns
+ * (wtfgpu_dirty_capacity = overlay_pages while there is no spill pool);
  * pages: the lane's current view of each (lane, gpa) page, 4096 bytes each. */
 int wtfgpu_read_gprs_list(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint64_t *out18);
 int wtfgpu_write_gprs_list(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, const uint64_t *in18);

@@ -70,6 +70,12 @@ class Write(C.Structure):
                 ("data_off", C.c_uint64)]
 
 
+class SpillStats(C.Structure):
+    """wtfgpu_spill_stats_t"""
+    _fields_ = [(k, C.c_uint64) for k in ("pool_pages", "lane_max", "in_use", "peak", "lanes_spilled",
+                                          "pool_empty", "claims")]
+
+
 SEG_ORDER = ["es", "cs", "ss", "ds", "fs", "gs", "tr", "ldtr"]
 GPR_ORDER = ["rax", "rcx", "rdx", "rbx", "rsp", "rbp", "rsi", "rdi",
              "r8", "r9", "r10", "r11", "r12", "r13", "r14", "r15"]
@@ -112,6 +118,13 @@ def load_hip_library(path: str = LIB_PATH) -> C.CDLL:
         "wtfgpu_load_pool": ([P, C.POINTER(U64), C.c_char_p, U64], C.c_int),
         "wtfgpu_alloc_lanes": ([P, U32, U32, U32], C.c_int),
         "wtfgpu_lane_count": ([P], U32),
+        "wtfgpu_alloc_spill": ([P, U64, U32], C.c_int),
+        "wtfgpu_dirty_capacity": ([P], U32),
+        "wtfgpu_overlay_pages": ([P], U32),
+        "wtfgpu_spill_stats": ([P, C.POINTER(SpillStats)], C.c_int),
+        "wtfgpu_read_dirty_list": ([P, C.POINTER(U32), U32, C.POINTER(U32)], C.c_int),
+        "wtfgpu_apply_phys_writes": ([P, C.POINTER(Write), U32, C.c_char_p, U64, C.POINTER(I32)], C.c_int),
+        "wtfgpu_restore_lanes": ([P, C.POINTER(U32), U32], C.c_int),
         "wtfgpu_set_initial_state": ([P, C.POINTER(Regs)], C.c_int),
         "wtfgpu_set_limit": ([P, U64], C.c_int),
         "wtfgpu_set_regroup": ([P, U64], C.c_int),

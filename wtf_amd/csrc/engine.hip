@@ -100,6 +100,12 @@ struct wtfgpu_ctx {
   u8 *d_lcopy = nullptr;      // the rare path's lane copies (LaneCopy)
   u32 *d_tlbok = nullptr;
   u8 *d_ovdata = nullptr;
+  // spill pool (wtfgpu_alloc_spill): pages, ownership bitmap, extension page
+  // indices, counters (the extension gpfns are d_ovgpfn's rows K..)
+  u8 *d_spdata = nullptr;
+  u32 *d_spmap = nullptr, *d_ovxpage = nullptr;
+  unsigned long long *d_spstat = nullptr;
+  u64 sp_pages = 0;
   wtfgpu_regs_t *d_full = nullptr;  // full per-lane architectural state (cold fields)
   // breakpoints
   u64 *d_bp = nullptr;
@@ -464,6 +470,19 @@ int wtfgpu_create(int device, wtfgpu_ctx **out) {
 
 void *wtfgpu_stream(wtfgpu_ctx *c) { return c ? (void *)c->q->stream : nullptr; }
 
+static void free_spill(wtfgpu_ctx *c) {
+  dfree(c->d_spdata);
+  dfree(c->d_spmap);
+  dfree(c->d_ovxpage);
+  dfree(c->d_spstat);
+  c->sp_pages = 0;
+  Dev &P = c->P;
+  P.X = P.sp_words = 0;
+  P.sp_data = nullptr;
+  P.sp_map = P.ovx_gpfn = P.ovx_page = nullptr;
+  P.sp_stat = nullptr;
+}
+
 static void free_lanes(wtfgpu_ctx *c) {
   dfree(c->d_feedpos);  // sized by the lane count
   dfree(c->d_feedend);
@@ -507,6 +526,7 @@ static void free_lanes(wtfgpu_ctx *c) {
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tn), &T, sizeof(T));
   }
   dfree(c->d_ovdata);
+  free_spill(c);
   dfree(c->d_full);
   dfree(c->d_perm);
   // regrouping buffers are sized by the lane count: every queue's
@@ -516,6 +536,76 @@ static void free_lanes(wtfgpu_ctx *c) {
   dfree(c->d_lanegen);
   dfree(c->d_covcnt);
   dfree(c->d_covovf);
+}
+
+// The spill pool sits on top of the lane storage: allocated after
+// wtfgpu_alloc_lanes, dropped with it. Lanes that hold pool pages must have
+// been restored (or are about to be discarded with the lanes).
+int wtfgpu_alloc_spill(wtfgpu_ctx *c, uint64_t pool_pages, uint32_t lane_max) {
+  if (!c || !c->P.nlanes || !c->d_ovgpfn) return WTFGPU_ERR_INVALID;
+  if ((pool_pages == 0) != (lane_max == 0) || pool_pages > 0xffffffe0ull) return WTFGPU_ERR_INVALID;
+  HIPCHK(hipSetDevice(c->device));
+  for (QueueRes &q : c->queues)
+    if (q.stream) HIPCHK(hipStreamSynchronize(q.stream));
+  Dev &P = c->P;
+  const u64 N = P.nlanes;
+  // a pool that is replaced must be empty (its owners' lists would dangle)
+  if (c->d_spstat) {
+    unsigned long long st[SP_NSTAT];
+    HIPCHK(hipMemcpy(st, c->d_spstat, sizeof(st), hipMemcpyDeviceToHost));
+    if (st[SP_INUSE]) return WTFGPU_ERR_INVALID;
+  }
+  free_spill(c);
+  // the dirty list keeps one allocation: K rows, then the X extension rows
+  u32 *gp = nullptr;
+  if (dalloc(&gp, ((u64)P.K + lane_max) * N)) return WTFGPU_ERR_OOM;
+  HIPCHK(hipMemcpy(gp, c->d_ovgpfn, (u64)P.K * N * 4, hipMemcpyDeviceToDevice));
+  dfree(c->d_ovgpfn);
+  c->d_ovgpfn = P.ov_gpfn = gp;
+  if (!pool_pages) return WTFGPU_OK;
+  const u64 words = (pool_pages + 31) / 32;
+  int rc = dalloc(&c->d_spdata, pool_pages * WTFGPU_PAGE_SIZE);
+  rc |= dalloc(&c->d_spmap, words);
+  rc |= dalloc(&c->d_ovxpage, (u64)lane_max * N);
+  rc |= dalloc(&c->d_spstat, (u64)SP_NSTAT);
+  if (rc || ((uintptr_t)c->d_spdata & 0xfff)) {
+    free_spill(c);
+    return WTFGPU_ERR_OOM;
+  }
+  std::vector<u32> map(words, 0);  // bits past the last page stay owned for ever
+  if (pool_pages & 31) map[words - 1] = ~0u << (pool_pages & 31);
+  HIPCHK(hipMemcpy(c->d_spmap, map.data(), words * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(c->d_spstat, 0, SP_NSTAT * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(c->d_ovxpage, 0, (u64)lane_max * N * 4));
+  c->sp_pages = pool_pages;
+  P.X = lane_max;
+  P.sp_words = (u32)words;
+  P.sp_data = c->d_spdata;
+  P.sp_map = c->d_spmap;
+  P.ovx_gpfn = c->d_ovgpfn + (u64)P.K * N;
+  P.ovx_page = c->d_ovxpage;
+  P.sp_stat = c->d_spstat;
+  return WTFGPU_OK;
+}
+
+uint32_t wtfgpu_dirty_capacity(wtfgpu_ctx *c) { return c ? c->P.K + c->P.X : 0; }
+
+int wtfgpu_spill_stats(wtfgpu_ctx *c, wtfgpu_spill_stats_t *out) {
+  if (!c || !out) return WTFGPU_ERR_INVALID;
+  memset(out, 0, sizeof(*out));
+  if (!c->d_spstat) return WTFGPU_OK;  // no pool: all zero
+  HIPCHK(hipSetDevice(c->device));
+  unsigned long long st[SP_NSTAT];  // (on the queue's stream: after its queued runs and restores)
+  HIPCHK(hipMemcpyAsync(st, c->d_spstat, sizeof(st), hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
+  out->pool_pages = c->sp_pages;
+  out->lane_max = c->P.X;
+  out->in_use = st[SP_INUSE];
+  out->peak = st[SP_PEAK];
+  out->lanes_spilled = st[SP_LANES];
+  out->pool_empty = st[SP_EMPTY];
+  out->claims = st[SP_CLAIMS];
+  return WTFGPU_OK;
 }
 
 int wtfgpu_destroy(wtfgpu_ctx *c) {
@@ -1612,7 +1702,7 @@ int wtfgpu_read_dirty_list(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uin
   if (int rc = check_lane_list(c, lanes, n)) return rc;
   if (n == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  Side o = side_room((u64)n * ((u64)c->P.K + 1) * 4);
+  Side o = side_room((u64)n * ((u64)c->P.K + c->P.X + 1) * 4);
   if (int rc = stage_lanes(c, Upload::Direct, lanes, n, &o, 1)) return rc;
   u8 *const S = c->q->d_scratch;
   k_gather_dirty<<<(n + 255) / 256, 256, 0, c->q->stream>>>(c->P, (const u32 *)S, n, (u32 *)(S + o.off));

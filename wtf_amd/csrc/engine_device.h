@@ -142,7 +142,21 @@ struct Dev {
   u64 cr3_0;             // the testcases' initial cr3 (Cr3Change_t, bochscpu_backend.cc:628-657)
   u64 limit;
   u64 *stat;             // [0] group steps, [1] retired, [2] lanes still running
+  // spill pool (wtfgpu_alloc_spill; X == 0: off). A lane's dirty pages past
+  // its K private slots live in pool pages it claims; ov_count keeps counting
+  // all of them, so dirty slot k >= K is extension entry k - K. ov_gpfn's
+  // allocation then has K + X rows and ovx_gpfn points at its row K: the
+  // whole dirty list is one [K + X][nlanes] array.
+  u32 X;                 // pool pages a lane may hold (its cap is K + X dirty pages)
+  u32 sp_words;          // words of sp_map
+  u8 *sp_data;           // [S][4096]
+  u32 *sp_map;           // one bit per pool page, set = owned (tail bits past S stay set)
+  u32 *ovx_gpfn;         // [X][nlanes]
+  u32 *ovx_page;         // [X][nlanes]: pool page index of each extension entry
+  unsigned long long *sp_stat;  // SP_* counters
 };
+
+enum { SP_INUSE = 0, SP_PEAK, SP_LANES, SP_EMPTY, SP_CLAIMS, SP_NSTAT };
 
 // ---------------------------------------------------------------- helpers
 __device__ __forceinline__ u64 rfl64(u64 v) {

@@ -105,15 +105,137 @@ __device__ __forceinline__ void set_cs(Lane &L, LaneSys &S, u32 sel) {
 // ------------------------------------------------------------------ physical memory
 __device__ __forceinline__ u64 bloom_bit(u64 gpfn) { return 1ull << ((gpfn * 0x9E3779B97F4A7C15ull) >> 58); }
 
+// ------------------------------------------------------------------ spill pool
+// A lane whose K private slots are full takes further copy-on-write pages
+// from a device-wide pool (Dev::sp_data), up to X of them. The rules that
+// keep this correct on a chip whose XCD L2s are not coherent with each other
+// and whose L1s are never refreshed by another CU's stores:
+//  1. A page is claimed and released only by agent-scope atomics on its bit
+//     of sp_map (claim: fetch-or, owned when the bit was clear before; release:
+//     fetch-and). No free list, so no ABA: a bit says nothing but "owned".
+//  2. Only the restore kernels release (spill_release). They run on the
+//     stream that ran the lane's last k_run, so the owner's stores were
+//     written back at that kernel's end before anyone can claim the page
+//     again. Nothing releases inside k_run or the host-write kernels.
+//  3. The claimer overwrites the whole page (the copy-on-write copy) before it
+//     reads any of it, so a stale clean line an earlier owner left in some L2
+//     is never observed. spill_alloc's caller copies before the dirty count
+//     grows; until then no lookup can return the page.
+//  4. Only the owning lane (or a host kernel acting for it between its
+//     launches) touches a pool page's data.
+#ifdef WTFGPU_HOST_SIM  // one thread: plain read-modify-write
+__device__ __forceinline__ u32 sp_load(const u32 *p) { return *p; }
+__device__ __forceinline__ u32 sp_or(u32 *p, u32 v) { const u32 o = *p; *p = o | v; return o; }
+__device__ __forceinline__ void sp_and(u32 *p, u32 v) { *p &= v; }
+__device__ __forceinline__ u64 sp_add(unsigned long long *p, u64 v) { const u64 o = *p; *p = o + v; return o; }
+__device__ __forceinline__ void sp_max(unsigned long long *p, u64 v) { if (*p < v) *p = v; }
+#else
+__device__ __forceinline__ u32 sp_load(const u32 *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ u32 sp_or(u32 *p, u32 v) {
+  return __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void sp_and(u32 *p, u32 v) {
+  __hip_atomic_fetch_and(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ u64 sp_add(unsigned long long *p, u64 v) {
+  return __hip_atomic_fetch_add(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void sp_max(unsigned long long *p, u64 v) {
+  __hip_atomic_fetch_max(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+#endif
+
+// Claim one pool page for `lane`: scan the bitmap from a lane-hashed word,
+// try the first clear bit of each word. ~0u = no clear bit in a whole pass
+// (pool empty at this moment: counted, not reproducible from a seed).
+__device__ __noinline__ u32 spill_claim(const Dev &P, u32 lane) {
+  const u32 nw = P.sp_words;
+  u32 w = (u32)((lane * 0x9E3779B1u) % nw);
+  for (u32 i = 0; i < nw; i++) {
+    u32 v = sp_load(&P.sp_map[w]);
+    while (v != ~0u) {
+      const u32 bit = 1u << __builtin_ctz(~v);
+      const u32 old = sp_or(&P.sp_map[w], bit);
+      if (!(old & bit)) {
+        const u64 now = sp_add(&P.sp_stat[SP_INUSE], 1) + 1;
+        sp_max(&P.sp_stat[SP_PEAK], now);
+        sp_add(&P.sp_stat[SP_CLAIMS], 1);
+        return w * 32 + (u32)__builtin_ctz(bit);
+      }
+      v = old | bit;
+    }
+    w = w + 1 == nw ? 0 : w + 1;
+  }
+  sp_add(&P.sp_stat[SP_EMPTY], 1);
+  return ~0u;
+}
+
+// Dirty slot `slot` >= K of `lane`: a pool page, entered in the lane's
+// extension list. nullptr = the lane holds K + X pages already (deterministic
+// per testcase) or the pool is empty (not). The caller fills the page before
+// it raises the lane's dirty count (rule 3).
+__device__ __noinline__ u8 *spill_alloc(const Dev &P, u32 lane, u32 slot) {
+  const u32 x = slot - P.K;
+  if (x >= P.X) return nullptr;
+  const u32 pg = spill_claim(P, lane);
+  if (pg == ~0u) return nullptr;
+  P.ovx_page[(u64)x * P.nlanes + lane] = pg;
+  if (x == 0) sp_add(&P.sp_stat[SP_LANES], 1);
+  return P.sp_data + (u64)pg * WTFGPU_PAGE_SIZE;
+}
+
+// Where the lane's next copy-on-write page goes (slot = its dirty count):
+// every site that takes a new overlay slot asks here. nullptr = none left
+// (WTFGPU_EXIT_OVERLAY_FULL / WTFGPU_ERR_OOM at the caller).
+__device__ __forceinline__ u8 *ov_alloc(const Dev &P, u32 lane, u32 slot) {
+  if (slot < P.K) return P.ov_data + ((u64)lane * P.K + slot) * WTFGPU_PAGE_SIZE;
+  return spill_alloc(P, lane, slot);
+}
+
+// The extension list's part of phys_page: the lane's pool copy of gpfn, or
+// nullptr. Kept out of line so the walk inlined into the fast loop stays small.
+__device__ __noinline__ const u8 *spill_find(const Dev &P, u32 lane, u32 ovn, u32 gpfn) {
+  for (u32 x = 0; x < ovn - P.K; x++) {
+    if (P.ovx_gpfn[(u64)x * P.nlanes + lane] == gpfn)
+      return P.sp_data + (u64)P.ovx_page[(u64)x * P.nlanes + lane] * WTFGPU_PAGE_SIZE;
+  }
+  return nullptr;
+}
+
+// Restore's part: the pool pages of a lane that held `cnt` dirty pages go
+// back (rule 2). One compare for a lane that never spilled.
+__device__ __forceinline__ void spill_release(const Dev &P, u32 lane, u32 cnt) {
+  if (cnt <= P.K) return;
+  for (u32 x = 0; x < cnt - P.K; x++) {
+    const u32 pg = P.ovx_page[(u64)x * P.nlanes + lane];
+    sp_and(&P.sp_map[pg >> 5], ~(1u << (pg & 31)));
+  }
+  sp_add(&P.sp_stat[SP_INUSE], (u64)0 - (cnt - P.K));
+}
+
 // Lane view of a guest physical page: private overlay copy if the lane wrote
-// it, else the snapshot pool page, else the zero page (bochscpu_backend.cc:124-131).
+// it (one of its K slots, or past them a pool page), else the snapshot pool
+// page, else the zero page (bochscpu_backend.cc:124-131). The extension list
+// is scanned only when the lane has spilled and the bloom bit hits.
+// kSpill = false is the fast loop's form (k_run's registers stay as they
+// are): for callers that made sure that ovn <= K, the loop as it always was.
+template <bool kSpill = true>
 __device__ __forceinline__ const u8 *phys_page(const Dev &P, u32 lane, u32 ovn, u64 bloom, u64 gpfn, bool &priv) {
   priv = false;
   if (bloom & bloom_bit(gpfn)) {
-    for (u32 k = 0; k < ovn; k++) {
+    const u32 nk = !kSpill || ovn < P.K ? ovn : P.K;
+    for (u32 k = 0; k < nk; k++) {
       if (P.ov_gpfn[(u64)k * P.nlanes + lane] == (u32)gpfn) {
         priv = true;
         return P.ov_data + ((u64)lane * P.K + k) * WTFGPU_PAGE_SIZE;
+      }
+    }
+    if (kSpill && ovn > P.K) {
+      if (const u8 *p = spill_find(P, lane, ovn, (u32)gpfn)) {
+        priv = true;
+        return p;
       }
     }
   }
@@ -178,7 +300,8 @@ __device__ __forceinline__ bool perm_ok(const Lane &L, u64 td, int acc) {
 // 4-level walk through the lane's physical view (kdmp-parser.h:269-345 shape,
 // SDM permission bits accumulated). No A/D updates (U8). Faults set on L
 // (kFault); without kFault a walk that would fault only returns false.
-template <bool kFault = true>
+// kSpill = false: the fast loop's form, for a lane with ovn <= K (phys_page).
+template <bool kFault = true, bool kSpill = true>
 __device__ __forceinline__ bool walk(const Dev &P, Lane &L, u64 va, int acc, u64 &td, u64 &gpfn) {
   const bool nxe = (L.efer >> 11) & 1;
   if (!canonical(va)) {
@@ -191,7 +314,7 @@ __device__ __forceinline__ bool walk(const Dev &P, Lane &L, u64 va, int acc, u64
   bool priv;
   for (int level = 3; level >= 0; level--) {
     const u64 idx = (va >> (12 + 9 * level)) & 0x1ff;
-    const u8 *pg = phys_page(P, L.lane, L.ovn, L.bloom, table >> 12, priv);
+    const u8 *pg = phys_page<kSpill>(P, L.lane, L.ovn, L.bloom, table >> 12, priv);
     e = *(const u64 *)(pg + idx * 8);
     if (!(e & 1)) {
       if (kFault) set_fault(L, WTFGPU_VEC_PF, pf_error(L, acc, false), va);
@@ -208,7 +331,7 @@ __device__ __forceinline__ bool walk(const Dev &P, Lane &L, u64 va, int acc, u64
   }
   const u64 gpa = ((e & 0x000ffffffffff000ull) & ~pmask) | (va & pmask);
   gpfn = gpa >> 12;
-  const u8 *pg = phys_page(P, L.lane, L.ovn, L.bloom, gpfn, priv);
+  const u8 *pg = phys_page<kSpill>(P, L.lane, L.ovn, L.bloom, gpfn, priv);
   td = (u64)(uintptr_t)pg | (aw ? T_W : 0) | (au ? T_U : 0) | (nx ? T_NX : 0) | (priv ? T_PRIV : 0) |
        (is_ptpage(P, gpfn) ? T_PT : 0);
   return true;
@@ -217,9 +340,9 @@ __device__ __forceinline__ bool walk(const Dev &P, Lane &L, u64 va, int acc, u64
 // Copy-on-write into overlay slot `slot` of `lane`: the page joins the dirty
 // list (bochscpu_backend.cc:887-889 DirtyGpa; dropped again by restore :751-772).
 // One lane's copy (the slow path; k_run's fast loop copies with the whole
-// wave): 256 bytes in flight per round, 16 rounds.
-__device__ __forceinline__ u8 *cow_copy(const Dev &P, u32 lane, u32 slot, u64 gpfn, const u8 *src) {
-  u8 *dst = P.ov_data + ((u64)lane * P.K + slot) * WTFGPU_PAGE_SIZE;
+// wave): 256 bytes in flight per round, 16 rounds. dst: the slot's page, from
+// ov_alloc (a private slot or a pool page; the dirty list row is the same).
+__device__ __forceinline__ u8 *cow_copy(const Dev &P, u32 lane, u32 slot, u64 gpfn, const u8 *src, u8 *dst) {
   const uint4 *__restrict__ s4 = (const uint4 *)src;
   uint4 *__restrict__ d4 = (uint4 *)dst;
   for (int i = 0; i < 256; i += 16) {
@@ -243,11 +366,12 @@ __device__ __forceinline__ bool service_miss(const Dev &P, Lane &L, u64 va, int 
     return false;
   }
   if (acc == ACC_W && !(td & T_PRIV)) {
-    if (L.ovn >= P.K) {
+    u8 *np = ov_alloc(P, L.lane, L.ovn);
+    if (!np) {
       L.status = WTFGPU_EXIT_OVERLAY_FULL;
       return false;
     }
-    u8 *np = cow_copy(P, L.lane, L.ovn, gpfn, (const u8 *)(uintptr_t)(td & ~0xfffull));
+    cow_copy(P, L.lane, L.ovn, gpfn, (const u8 *)(uintptr_t)(td & ~0xfffull), np);
     L.ovn++;
     L.bloom |= bloom_bit(gpfn);
     tlb_flush(L);  // other vpns may alias the old page
@@ -255,6 +379,14 @@ __device__ __forceinline__ bool service_miss(const Dev &P, Lane &L, u64 va, int 
   }
   tlb_put(L, va >> 12, td);
   return true;
+}
+
+// The fast loop's walk: one that would fault declines (false), and so does
+// every walk of a lane that has spilled (ovn > K): the slow step serves those
+// through the extension list, which the fast loop never scans (no call and no
+// second loop in the walks inlined there).
+__device__ __forceinline__ bool fast_walk(const Dev &P, Lane &L, u64 va, int acc, u64 &td, u64 &gpfn) {
+  return L.ovn <= P.K && walk<false, false>(P, L, va, acc, td, gpfn);
 }
 
 // The fast loop's own miss service (k_run): the TLB fill or first-write copy
@@ -266,10 +398,11 @@ __device__ __forceinline__ bool fast_fill(const Dev &P, Lane &L) {
   const u64 va = L.miss_va;
   const int acc = (int)L.miss_acc;
   u64 td, gpfn;
-  if (!walk<false>(P, L, va, acc, td, gpfn) || !perm_ok(L, td, acc)) return false;
+  if (!fast_walk(P, L, va, acc, td, gpfn) || !perm_ok(L, td, acc)) return false;
   if (acc == ACC_W && !(td & T_PRIV)) {
-    if ((td & T_PT) || L.ovn >= P.K) return false;
-    u8 *np = cow_copy(P, L.lane, L.ovn, gpfn, (const u8 *)(uintptr_t)(td & ~0xfffull));
+    if ((td & T_PT) || L.ovn >= P.K) return false;  // (past K the slow step allocates)
+    u8 *np = P.ov_data + ((u64)L.lane * P.K + L.ovn) * WTFGPU_PAGE_SIZE;
+    cow_copy(P, L.lane, L.ovn, gpfn, (const u8 *)(uintptr_t)(td & ~0xfffull), np);
     L.ovn++;
     L.bloom |= bloom_bit(gpfn);
     tlb_flush(L);  // other vpns may alias the old page
@@ -288,7 +421,7 @@ __device__ __forceinline__ bool fast_fill_prep(const Dev &P, Lane &L, u64 &src, 
   const u64 va = L.miss_va;
   const int acc = (int)L.miss_acc;
   dst = 0;
-  if (!walk<false>(P, L, va, acc, td, gpfn) || !perm_ok(L, td, acc)) return false;
+  if (!fast_walk(P, L, va, acc, td, gpfn) || !perm_ok(L, td, acc)) return false;
   if (acc == ACC_W && !(td & T_PRIV)) {
     if ((td & T_PT) || L.ovn >= P.K) return false;
     src = td & ~0xfffull;
@@ -307,7 +440,8 @@ __device__ __forceinline__ void fast_fault(const Dev &P, Lane &L) {
   const u64 va = L.miss_va;
   const int acc = (int)L.miss_acc;
   u64 td, gpfn;
-  if (!walk(P, L, va, acc, td, gpfn)) return;  // (walk<true> set the fault)
+  if (L.ovn > P.K) return;  // a spilled lane: fast_walk declined, the slow step raises what there is to raise
+  if (!walk<true, false>(P, L, va, acc, td, gpfn)) return;  // (walk<true> set the fault)
   if (!perm_ok(L, td, acc)) set_fault(L, WTFGPU_VEC_PF, pf_error(L, acc, true), va);
 }
 __device__ __forceinline__ void fast_fill_finish(const Dev &P, Lane &L, u64 dst, u64 gpfn, u64 td) {

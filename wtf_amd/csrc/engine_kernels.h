@@ -31,6 +31,7 @@ __device__ __forceinline__ void restore_lane(const Dev &P, const InitState &s, c
   P.status[lane] = WTFGPU_RUNNING;
   P.lflags[lane] = 0;
   P.sys[lane] = s.sys;
+  spill_release(P, lane, P.ov_count[lane]);  // pool pages back (the one place: engine_exec.h rule 2)
   P.ov_count[lane] = 0;
   tlb_stale(P, lane);
   if (P.rd_seed) P.rd_seed[lane] = P.rd_seed0;  // bochscpu_backend.cc:1030
@@ -76,6 +77,7 @@ __global__ void k_restore(Dev P, const InitState *S, const wtfgpu_regs_t *full0,
   P.status[lane] = WTFGPU_RUNNING;
   P.lflags[lane] = 0;
   P.sys[lane] = s.sys;
+  spill_release(P, lane, P.ov_count[lane]);  // pool pages back (the one place: engine_exec.h rule 2)
   P.ov_count[lane] = 0;  // the dirty-list reset: overlays dropped, nothing copied
   tlb_stale(P, lane);
   if (P.rd_seed) P.rd_seed[lane] = P.rd_seed0;  // bochscpu_backend.cc:1030
@@ -150,8 +152,13 @@ __device__ __forceinline__ bool lane_phys_write_block(const Dev &P, Lane &L, u64
     const u8 *pg = phys_page(P, L.lane, L.ovn, L.bloom, gpa >> 12, priv);
     u8 *dst = (u8 *)pg;
     if (!priv) {
-      if (L.ovn >= P.K) return false;
-      dst = P.ov_data + ((u64)L.lane * P.K + L.ovn) * WTFGPU_PAGE_SIZE;
+      // one thread takes the slot (a pool page past K: one claim), all copy
+      __shared__ u8 *slot_page;
+      if (lid == 0) slot_page = ov_alloc(P, L.lane, L.ovn);
+      __syncthreads();
+      dst = slot_page;
+      __syncthreads();  // (read before the next round's write)
+      if (!dst) return false;
       const uint4 *s4 = (const uint4 *)pg;
       uint4 *d4 = (uint4 *)dst;
       for (u32 i = lid; i < 256; i += 64) d4[i] = s4[i];
@@ -233,6 +240,11 @@ __global__ void k_inject_fault(Dev P, const u32 *lanes, const u64 *addrs, u32 n,
     store_lane(P, L);
     tlb_stale(P, lane);
     P.lflags[lane] = 0;
+  } else if (L.ovn > P.K && L.ovn != P.ov_count[lane]) {
+    // the failed delivery claimed pool pages for the frame: they stay on the
+    // lane's list (as k_run keeps them), so restore gives them back
+    P.ov_count[lane] = L.ovn;
+    tlb_stale(P, lane);
   }
 }
 
@@ -332,14 +344,15 @@ __global__ void k_scatter_gprs(Dev P, const u32 *lanes, u32 n, const u64 *in) {
   P.rip[l] = in[(u64)t * 18 + 16];
   P.rflags[l] = in[(u64)t * 18 + 17];
 }
-// Dirty lists of a lane list: out[t * (K + 1)] = count, then the gpfns.
+// Dirty lists of a lane list: out[t * (K + X + 1)] = count, then the gpfns
+// (ov_gpfn's rows run on into the extension list).
 __global__ void k_gather_dirty(Dev P, const u32 *lanes, u32 n, u32 *out) {
   const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   const u32 l = lanes[t], cnt = P.ov_count[l];
-  u32 *o = out + (u64)t * (P.K + 1);
+  u32 *o = out + (u64)t * (P.K + P.X + 1);
   o[0] = cnt;
-  for (u32 k = 0; k < cnt && k < P.K; k++) o[1 + k] = P.ov_gpfn[(u64)k * P.nlanes + l];
+  for (u32 k = 0; k < cnt && k < P.K + P.X; k++) o[1 + k] = P.ov_gpfn[(u64)k * P.nlanes + l];
 }
 // Lane views of physical pages (overlay copy, else snapshot, else zeros): one
 // 256-thread block per (lane, gpa) request, 16 bytes per thread.

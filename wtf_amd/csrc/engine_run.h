@@ -368,8 +368,9 @@ __device__ __forceinline__ bool lane_phys_write(const Dev &P, Lane &L, u64 gpa, 
     const u8 *pg = phys_page(P, L.lane, L.ovn, L.bloom, gpa >> 12, priv);
     u8 *dst = (u8 *)pg;
     if (!priv) {
-      if (L.ovn >= P.K) return false;
-      dst = cow_copy(P, L.lane, L.ovn, gpa >> 12, pg);
+      dst = ov_alloc(P, L.lane, L.ovn);
+      if (!dst) return false;
+      cow_copy(P, L.lane, L.ovn, gpa >> 12, pg, dst);
       L.ovn++;
       L.bloom |= bloom_bit(gpa >> 12);
     }
@@ -387,8 +388,9 @@ __device__ __forceinline__ bool lane_phys_write64(const Dev &P, Lane &L, u64 gpa
   const u8 *pg = phys_page(P, L.lane, L.ovn, L.bloom, gpa >> 12, priv);
   u8 *dst = (u8 *)pg;
   if (!priv) {
-    if (L.ovn >= P.K) return false;
-    dst = cow_copy(P, L.lane, L.ovn, gpa >> 12, pg);
+    dst = ov_alloc(P, L.lane, L.ovn);
+    if (!dst) return false;
+    cow_copy(P, L.lane, L.ovn, gpa >> 12, pg, dst);
     L.ovn++;
     L.bloom |= bloom_bit(gpa >> 12);
   }
@@ -1233,7 +1235,7 @@ __global__ __launch_bounds__(256, 2) void k_run(Dev P, u32 first, u32 count, u64
         if (in_mask(cxm)) {
           u64 td, gp;
           bool ok = tlb_get(L, grip >> 12, td) && perm_ok(L, td, ACC_X);
-          if (!ok && walk<false>(P, L, grip & ~0xfffull, ACC_X, td, gp) && perm_ok(L, td, ACC_X)) {
+          if (!ok && fast_walk(P, L, grip & ~0xfffull, ACC_X, td, gp) && perm_ok(L, td, ACC_X)) {
             tlb_put(L, grip >> 12, td);
             ok = true;
           }

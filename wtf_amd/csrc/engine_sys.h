@@ -66,11 +66,12 @@ __device__ __forceinline__ bool sup_write_pa(const Dev &P, Lane &L, u64 gpa, u64
   const u8 *pg = phys_page(P, L.lane, L.ovn, L.bloom, gpa >> 12, priv);
   u8 *dst = (u8 *)pg;
   if (!priv) {
-    if (L.ovn >= P.K) {
+    dst = ov_alloc(P, L.lane, L.ovn);
+    if (!dst) {
       L.status = WTFGPU_EXIT_OVERLAY_FULL;
       return false;
     }
-    dst = cow_copy(P, L.lane, L.ovn, gpa >> 12, pg);
+    cow_copy(P, L.lane, L.ovn, gpa >> 12, pg, dst);
     L.ovn++;
     L.bloom |= bloom_bit(gpa >> 12);
     L.flush = 1;  // cached translations may point at the shared copy

@@ -50,6 +50,28 @@ class Engine:
         _chk(self.L.wtfgpu_alloc_lanes(self.ctx, n, overlay_pages, cov_entries), "alloc_lanes")
         self.nlanes = n
 
+    def alloc_spill(self, pool_pages, lane_max):
+        """A device-wide pool of pool_pages copy-on-write pages for lanes whose
+        overlay_pages private ones are full, lane_max of them per lane at most
+        (wtfgpu_alloc_spill; after alloc_lanes)."""
+        _chk(self.L.wtfgpu_alloc_spill(self.ctx, pool_pages, lane_max), "alloc_spill")
+
+    def spill_stats(self) -> dict:
+        """The pool's counters: pool_pages, lane_max, in_use, peak,
+        lanes_spilled, pool_empty, claims (all zero without a pool)."""
+        st = abi.SpillStats()
+        _chk(self.L.wtfgpu_spill_stats(self.ctx, C.byref(st)), "spill_stats")
+        return {k: getattr(st, k) for k, _ in abi.SpillStats._fields_}
+
+    def dirty_capacity(self) -> int:
+        """Dirty pages a lane can hold: overlay_pages + the spill cap."""
+        return self.L.wtfgpu_dirty_capacity(self.ctx)
+
+    def restore_lanes(self, lanes):
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        _chk(self.L.wtfgpu_restore_lanes(self.ctx, la.ctypes.data_as(C.POINTER(C.c_uint32)), len(la)),
+             "restore_lanes")
+
     def set_initial_state(self, regs: abi.Regs):
         _chk(self.L.wtfgpu_set_initial_state(self.ctx, C.byref(regs)), "set_initial_state")
 
@@ -156,17 +178,31 @@ class Engine:
         _chk(self.L.wtfgpu_stop(self.ctx, la, n, status), "stop")
 
     # ---- memory
-    def apply_writes(self, writes):
-        """writes: list of (lane, gva, bytes)."""
+    def apply_writes(self, writes, phys=False, check=True):
+        """writes: list of (lane, gva, bytes); phys: the addresses are guest
+        physical (wtfgpu_apply_phys_writes). Returns each write's status;
+        check=False returns them also when a write failed instead of raising."""
         if not writes:
-            return
+            return []
         recs = (abi.Write * len(writes))()
         blob = bytearray()
         for i, (lane, gva, data) in enumerate(writes):
             recs[i].lane, recs[i].len, recs[i].gva, recs[i].data_off = lane, len(data), gva, len(blob)
             blob += data
         st = (C.c_int32 * len(writes))()
-        _chk(self.L.wtfgpu_apply_writes(self.ctx, recs, len(writes), bytes(blob), len(blob), st), "apply_writes")
+        fn = self.L.wtfgpu_apply_phys_writes if phys else self.L.wtfgpu_apply_writes
+        rc = fn(self.ctx, recs, len(writes), bytes(blob), len(blob), st)
+        if check:
+            _chk(rc, "apply_writes")
+        return list(st)
+
+    def dirty_list(self, lanes) -> np.ndarray:
+        """[n, dirty_capacity + 1] u32: each lane's dirty count, then its gpfns."""
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        out = np.zeros((len(la), self.dirty_capacity() + 1), dtype=np.uint32)
+        _chk(self.L.wtfgpu_read_dirty_list(self.ctx, la.ctypes.data_as(C.POINTER(C.c_uint32)), len(la),
+                                           out.ctypes.data_as(C.POINTER(C.c_uint32))), "read_dirty_list")
+        return out
 
     def read_virt(self, lane, gva, n) -> bytes:
         b = C.create_string_buffer(n)

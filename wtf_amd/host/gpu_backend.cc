@@ -84,6 +84,19 @@ bool GpuBackend_t::Initialize(const Options_t &Opts, const CpuState_t &CpuState)
   nlanes_ = std::max<uint32_t>(Opts.GpuLanes, 1);
   overlay_pages_ = std::max<uint32_t>(Opts.GpuOverlayPages, 1);
   if (wtfgpu_alloc_lanes(ctx_, nlanes_, overlay_pages_, Opts.GpuCoverageSet)) return false;
+  // the spill pool: the options, else the environment (the way a node gets it)
+  uint64_t spill = Opts.GpuSpillPages;
+  uint32_t spill_max = Opts.GpuSpillLaneMax;
+  if (const char *e = getenv("WTFGPU_SPILL_PAGES"); e && !spill) spill = strtoull(e, nullptr, 0);
+  if (const char *e = getenv("WTFGPU_SPILL_LANE_MAX"); e && !spill_max) spill_max = (uint32_t)strtoul(e, nullptr, 0);
+  if (spill) {
+    if (!spill_max) spill_max = Options_t::kDefaultSpillLaneMax;
+    if (wtfgpu_alloc_spill(ctx_, spill, spill_max)) {
+      printf("wtfgpu_alloc_spill(%llu, %u) failed\n", (unsigned long long)spill, spill_max);
+      return false;
+    }
+  }
+  dirty_cap_ = wtfgpu_dirty_capacity(ctx_);
   views_.clear();
   views_.resize(nlanes_);
   touched_.assign(nlanes_, 0);
@@ -457,10 +470,10 @@ uint8_t *GpuBackend_t::lane_page(uint32_t lane, uint64_t gpfn) const {
   if (Staged *p = find_staged(lane, gpfn)) return p->data;
   LaneView &v = view(lane);
   if (!v.dirty_known) {
-    std::vector<uint32_t> buf(overlay_pages_ + 1);
+    std::vector<uint32_t> buf(dirty_cap_ + 1);
     std::lock_guard<std::mutex> g(engine_mu_);
     wtfgpu_read_dirty_list(ctx_, &lane, 1, buf.data());
-    v.dirty.assign(buf.begin() + 1, buf.begin() + 1 + std::min<uint32_t>(buf[0], overlay_pages_));
+    v.dirty.assign(buf.begin() + 1, buf.begin() + 1 + std::min<uint32_t>(buf[0], dirty_cap_));
     v.dirty_known = true;
   }
   if (in_overlay(v, gpfn)) {
@@ -881,7 +894,7 @@ bool GpuBackend_t::fill_lanes(const std::vector<uint32_t> &fin, uint32_t first, 
       r.rip = r.gprs[16];
       const uint32_t k = fin[i] - lo;
       r.bytes = nb[k];
-      r.dirty = std::min(dc[k], overlay_pages_);
+      r.dirty = std::min(dc[k], dirty_cap_);
       r.edges = ec[2 * k];
       r.edges_new = ec[2 * k + 1];
     }
@@ -954,7 +967,7 @@ bool GpuBackend_t::service_hits(const std::vector<uint32_t> &hits, uint32_t firs
     // the lanes' Rdrand chains (a device Rdrand action may have advanced them)
     std::vector<uint64_t> seeds(hits.size());
     if (wtfgpu_lane_seeds(ctx_, hits.data(), (uint32_t)hits.size(), seeds.data(), 0)) return false;
-    const uint32_t stride = overlay_pages_ + 1;
+    const uint32_t stride = dirty_cap_ + 1;
     std::vector<uint32_t> dl(hits.size() * stride);
     if (wtfgpu_read_dirty_list(ctx_, hits.data(), (uint32_t)hits.size(), dl.data())) return false;
     const auto t1 = Clock::now();
@@ -973,7 +986,7 @@ bool GpuBackend_t::service_hits(const std::vector<uint32_t> &hits, uint32_t firs
       v.cr_known = 0;  // an exception delivery or a cr write may have changed them
       v.win_len = 0;
       drop_staged(v);
-      const uint32_t cnt = std::min(dl[i * stride], overlay_pages_);
+      const uint32_t cnt = std::min(dl[i * stride], dirty_cap_);
       v.dirty.assign(dl.begin() + i * stride + 1, dl.begin() + i * stride + 1 + cnt);
       v.dirty_known = true;
       // the stack page is needed to learn (a breakpoint's first hit) or to
@@ -1239,7 +1252,7 @@ std::optional<TestcaseResult_t> GpuBackend_t::Run(const uint8_t *, const uint64_
     wtfgpu_read_edge_counts(ctx_, 0, 1, ecount);
     last_run_ = out[0];
     last_run_.bytes = nbytes;
-    last_run_.dirty = std::min(dcount, overlay_pages_);
+    last_run_.dirty = std::min(dcount, dirty_cap_);
     last_run_.edges = ecount[0];
     last_run_.edges_new = ecount[1];
   }
@@ -2128,6 +2141,16 @@ std::string GpuBackend_t::StatsJson() const {
            stats_.out_ms, stats_.fresh_ms, stats_.occ_ms, stats_.harvest_ms, (unsigned long long)stats_.prepared,
            device_attrib_ ? 1 : 0);
   r += b;
+  {  // the spill pool's counters (zero without one)
+    wtfgpu_spill_stats_t sp{};
+    if (ctx_ && dirty_cap_ > overlay_pages_) {  // (no engine call without a pool)
+      std::lock_guard<std::mutex> g(engine_mu_);
+      wtfgpu_spill_stats(ctx_, &sp);
+    }
+    snprintf(b, sizeof(b), ",\"spill_peak\":%llu,\"spill_lanes\":%llu,\"spill_pool_empty\":%llu",
+             (unsigned long long)sp.peak, (unsigned long long)sp.lanes_spilled, (unsigned long long)sp.pool_empty);
+    r += b;
+  }
   r += ",\"unimpl_ops\":" + stats_.unimpl_ops.json();
   r += ",\"unimpl_raw\":" + stats_.unimpl_ops.raw_json();
   b[0] = 0;

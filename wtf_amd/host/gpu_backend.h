@@ -325,6 +325,7 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   CpuState_t initial_{};
   wtfgpu_regs_t initial_regs_{};
   uint32_t nlanes_ = 0, overlay_pages_ = 0;
+  uint32_t dirty_cap_ = 0;  // wtfgpu_dirty_capacity: overlay_pages_ + the spill pool's lane maximum
   uint64_t limit_ = 0;
   mutable std::vector<LaneView> views_;
   mutable std::vector<uint8_t> touched_;  // view(lane) was taken since the lane's last reset_view

@@ -249,6 +249,8 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     else if (a == "--limit") O.limit = strtoull(next("--limit"), nullptr, 0);
     else if (a == "--lanes") O.lanes = (uint32_t)strtoul(next("--lanes"), nullptr, 0);
     else if (a == "--overlay-pages") O.overlay_pages = (uint32_t)strtoul(next("--overlay-pages"), nullptr, 0);
+    else if (a == "--spill-pages") O.spill_pages = strtoull(next("--spill-pages"), nullptr, 0);
+    else if (a == "--spill-lane-max") O.spill_lane_max = (uint32_t)strtoul(next("--spill-lane-max"), nullptr, 0);
     else if (a == "--runs") O.runs = strtoull(next("--runs"), nullptr, 0);
     else if (a == "--seconds") O.seconds = atof(next("--seconds"));
     else if (a == "--seed") O.seed = strtoull(next("--seed"), nullptr, 0);
@@ -294,7 +296,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
   }
   if (O.name.empty() || O.target.empty()) {
     fprintf(stderr, "usage: [run|fuzz|master] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
-                    "       [--lanes n] [--overlay-pages k] [--runs n] [--seconds s] [--seed s] [--full-coverage]\n"
+                    "       [--lanes n] [--overlay-pages k] [--spill-pages s [--spill-lane-max x]] [--runs n] [--seconds s] [--seed s] [--full-coverage]\n"
                     "       [--serial-mutation] [--slice-steps s] [--regroup-steps r] [--rank r --world n [--exchange host:port | --nccl-id-file f]]\n"
                     "       [--address tcp://ip:port|unix://path [--batched] [--nodes k]] [--edges] [--device-attrib]\n"
                     "       [--trace-path dir [--trace-type rip|cov|tenet] [--trace-cap n] [--tenet-cap bytes]] [--module-so m.so] [--serial]\n");
@@ -316,6 +318,8 @@ bool LoadTarget(const RunnerOptions &O, Options_t &Opts, CpuState_t &State) {
   Opts.GpuDevice = O.device;
   Opts.GpuLanes = O.lanes;
   Opts.GpuOverlayPages = O.overlay_pages;
+  Opts.GpuSpillPages = O.spill_pages;
+  Opts.GpuSpillLaneMax = O.spill_lane_max;
   // (the streaming replay reads whole sets as well: see RunnerMain)
   if (O.full_coverage || (O.mode == "run" && O.stream_run)) Opts.GpuCoverageSet = 8192;
   Opts.Fuzz.Seed = (uint32_t)O.seed;

@@ -200,6 +200,8 @@ struct RunnerOptions {
   uint64_t limit = 0;
   uint32_t lanes = 1;
   uint32_t overlay_pages = 32;
+  uint64_t spill_pages = 0;     // --spill-pages: the shared pool for lanes past overlay_pages (0: none)
+  uint32_t spill_lane_max = 0;  // --spill-lane-max: pool pages one lane may hold (0: the default)
   uint64_t runs = 0;         // fuzz: testcases; run: repetitions of each input (subcommands.cc:85-88)
   double seconds = 0;        // fuzz: wall-clock budget (0 = none)
   uint64_t seed = 1337;

@@ -193,6 +193,14 @@ struct Options_t {
   int GpuDevice = 0;
   uint32_t GpuLanes = 1;
   uint32_t GpuOverlayPages = 32;
+  // spill pool (wtfgpu_alloc_spill): GpuSpillPages pages shared by all lanes
+  // for the dirty pages a lane has beyond GpuOverlayPages, GpuSpillLaneMax of
+  // them per lane at most. 0 pages: no pool (the default). With pages and no
+  // lane maximum the maximum is kDefaultSpillLaneMax. The environment's
+  // WTFGPU_SPILL_PAGES / WTFGPU_SPILL_LANE_MAX count where these are 0.
+  uint64_t GpuSpillPages = 0;
+  uint32_t GpuSpillLaneMax = 0;
+  static constexpr uint32_t kDefaultSpillLaneMax = 480;
   // per-lane new-coverage set entries (wtfgpu_alloc_lanes; 3/4 usable): a
   // testcase's rips not yet in the aggregate; --full-coverage (parity mode,
   // every rip of the testcase) takes the larger set
