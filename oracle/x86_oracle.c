@@ -1931,6 +1931,7 @@ static void yput(orc_machine *m, u32 r, y256 v, int l256) {
 #include "x86_oracle_ext.inc"  /* BMI1 / BMI2 / ADX / MOVBE / CRC32, SSE4.2, AES, PCLMULQDQ (U45) */
 #include "x86_oracle_avx2x.inc" /* FMA3, F16C, AVX2 gathers (U46) */
 #include "x86_oracle_avx512.inc" /* the AVX-512 subset and the opmask instructions (U47) */
+#include "x86_oracle_avx512x.inc" /* the AVX-512 integer shuffles, permutes, shifts and widenings (U49) */
 
 /* two-source ops of one 128-bit lane (the legacy semantics); 0 = not one */
 static int vlane(u32 op, int pc, const x128 *a, const x128 *b, u8 imm, u64 cnt, x128 *r) {
@@ -2144,7 +2145,8 @@ static int exec_vex(orc_machine *m, insn *d) {
   const u32 op = d->op, r3 = d->reg & 7, map = d->opmap, vv = d->vvvv;
   const int pp = (int)d->vpp, l256 = (int)d->vl, mem = d->is_mem;
   const u8 imm = d->bytes[d->len - 1];
-  if (d->evex) return exec_evex(m, d);                 /* U47 */
+  if (d->evex) /* U47, else U49 */
+    return zform_of(map, op, pp, d->vw).kind != ZK_NONE ? exec_evex(m, d) : exec_evexx(m, d);
   if (kop_any(map, op, pp)) return exec_kop(m, d);
   if (fp_form_o(map, op, pp, 1)) return exec_fp(m, d); /* U39 / U40 */
   if (s4_form_o(map, op, pp, 1)) return exec_s4(m, d); /* U41 */
@@ -3433,6 +3435,7 @@ static int decode(orc_machine *m, insn *d, memref *mr) {
     d->pos = (u32)save;
   }
   zform ezf = {ZK_NONE, 0, 0, 0, 0, 0};
+  xform exf = xform_of(0, 0, 0, 0, -1);
   if (b == 0x62 && !d->m32) { /* EVEX (U47; 32-bit code's bound stays outside) */
     const u8 p0 = fetch8(m, d), p1 = fetch8(m, d), p2 = fetch8(m, d);
     b = fetch8(m, d);
@@ -3454,9 +3457,10 @@ static int decode(orc_machine *m, insn *d, memref *mr) {
     d->eaaa = p2 & 7u;
     d->op = b;
     ezf = zform_of(d->opmap, b, (int)d->vpp, d->vw);
+    if (ezf.kind == ZK_NONE) exf = xform_of(d->opmap, b, (int)d->vpp, d->vw, -1);
     /* maps 1-3 and 5-6 (AVX512-FP16) are defined: outside the subset is UNIMPLEMENTED */
     d->undef = d->vbad || d->opmap == 0 || d->opmap == 4 || d->opmap == 7;
-    if (d->undef || d->opmap > 3 || ezf.kind == ZK_NONE) {
+    if (d->undef || d->opmap > 3 || (ezf.kind == ZK_NONE && exf.kind == XK_NONE)) {
       d->len = d->pos;
       return 1;
     }
@@ -3615,7 +3619,7 @@ static int decode(orc_machine *m, insn *d, memref *mr) {
   }
   if (d->evex) {
     has_modrm = 1;
-    imm = d->opmap == 3;
+    imm = d->opmap == 3 || exf.has_imm;
   }
   if (has_modrm) {
     decode_modrm(m, d, mr);
@@ -3623,7 +3627,11 @@ static int decode(orc_machine *m, insn *d, memref *mr) {
     if (d->evex) { /* 5-bit registers; disp8 * N */
       d->reg |= d->er2 << 4;
       if (d->mod == 3) d->rm |= d->rexx << 4;
-      if (d->mod == 1) mr->disp *= zdisp_n(ezf, 16u << d->ell, d->eb);
+      if (d->mod == 1 && ezf.kind != ZK_NONE) mr->disp *= zdisp_n(ezf, 16u << d->ell, d->eb);
+      if (d->mod == 1 && ezf.kind == ZK_NONE) { /* U49: a group's form is known once /digit is */
+        exf = xform_of(d->opmap, b, (int)d->vpp, d->vw, (int)(d->reg & 7));
+        mr->disp *= xdisp_n(&exf, 16u << d->ell, d->eb);
+      }
     }
   }
   if (d->opmap == 0 && (b == 0xf6 || b == 0xf7) && ((d->reg & 7) <= 1)) imm = b == 0xf6 ? 1 : izsz;

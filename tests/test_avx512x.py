@@ -2,11 +2,13 @@
 arithmetic, shifts and rotates, in-lane shuffles, cross-lane permutes, the
 widening loads, the 128- / 256-bit block moves, mask <-> vector and vmovd / q.
 
-Native-execution vectors (tests/golden/gen_avx512x_vectors.py) pin the
-engine's device code built for the host, generic and through the fast-loop
-digest. The oracle does not execute these forms yet, so there
-is no oracle comparison here. The GPU runs the same vectors in
-tests/test_gpu_avx512x.py.
+Native-execution vectors (tests/golden/gen_avx512x_vectors.py) pin both sides:
+the oracle's restatement (oracle/x86_oracle_avx512x.inc) and the engine's
+device code built for the host, generic and through the fast-loop digest, each
+judged by the same check() on every case; the recorded routines
+(gen_avx512x_programs.py) run on both to their int3. With the oracle pinned
+here, the random programs' EVEX pool (tests/progfuzz.py) may compare the engine
+with it. The GPU runs the same vectors in tests/test_gpu_avx512x.py.
 """
 import ctypes as C
 import gzip
@@ -15,9 +17,10 @@ import os
 
 import pytest
 
-from tests.golden.gen_avx512_vectors import case_inputs, guard_window
+from tests.golden.gen_avx512_vectors import BOUND, case_inputs, guard_window
 from tests.golden.gen_avx512x_programs import GPR_INDEX, source
 from tests.golden.gen_avx512x_vectors import forms, lengths
+from tests.oracle_lib import Oracle
 from tests.test_avx512 import WIN, XCR0, address_space, case_regs, check, get_zmm, sim_full
 from tests.test_sse import CODE_VA, SimResult
 from wtf_amd.abi import EXIT_FAULT, EXIT_INT3, EXIT_UNIMPLEMENTED, Regs, regs_from_state
@@ -65,6 +68,43 @@ def sim_case(L, c, fast=False):
         return ("icount", out.icount, out.status, out.vector)
     return check(c, out.status, out.vector, out.error, out.addr, list(out.gpr), out.rflags, get_zmm(fin),
                  list(fin.k), bytes(out.win[:WIN]), zin, win)
+
+
+def oracle_case(c):
+    """One case through the oracle (oracle/x86_oracle_avx512x.inc), as
+    tests/test_avx512.py's oracle_case does for U47, with this file's inputs."""
+    buf_va = int(DOC["buf_va"], 16)
+    zin, win = inputs(c)
+    sp = address_space(bytes.fromhex(c["code"]) + b"\xcc", buf_va, win, c["guard"])
+    regs = regs_from_state(user_state(CODE_VA, 0, sp.cr3))
+    pfns, blob = sp.phys()
+    o = Oracle(pfns=pfns, blob=blob)
+    o.restore(case_regs(c, regs, zin))
+    ex = o.step()
+    if o.icount() != (0 if "fault" in c else 1):
+        return ("icount", o.icount(), ex.status, ex.vector)
+    r = o.regs()
+    g = c["guard"]
+    mem = (bytes(BOUND) if g == 2 else o.read_virt(buf_va, BOUND)) + \
+        (bytes(WIN - BOUND) if g == 1 else o.read_virt(buf_va + BOUND, WIN - BOUND))
+    return check(c, ex.status, ex.vector, ex.error, ex.addr, list(r.gpr), r.rflags, get_zmm(r), list(r.k), mem,
+                 zin, win)
+
+
+@pytest.mark.parametrize("chunk", range(2))
+def test_oracle_matches_native_avx512x(chunk):
+    """Every case of the vector file through the oracle, judged by the same
+    check() as the engine's host build: GPRs, RFLAGS, zmm0-31, k0-7, the
+    window, and for the guard and ud.* cases the fault's vector, error code
+    and address."""
+    assert len(DOC["cases"]) == 4453
+    cases = DOC["cases"][chunk::2]
+    fails = []
+    for c in cases:
+        bad = oracle_case(c)
+        if bad:
+            fails.append((c["name"], c["code"]) + bad)
+    assert not fails, f"{len(fails)}/{len(cases)} mismatches, first: {fails[:5]}"
 
 
 @pytest.mark.parametrize("fast", [False, True], ids=["exec", "fast"])
@@ -216,6 +256,13 @@ def test_evex_forms_outside_the_subset_stay_unimplemented(name):
                        C.byref(fin), None)
         assert out.status == EXIT_UNIMPLEMENTED and out.status not in (EXIT_FAULT, EXIT_INT3), (name, out.status,
                                                                                                   out.vector)
+    # the oracle ends them the same way, with nothing retired and nothing changed
+    o = Oracle(pfns=pfns, blob=blob)
+    o.restore(regs)
+    ex = o.step()
+    assert (ex.status, o.icount()) == (EXIT_UNIMPLEMENTED, 0), (name, ex.status, ex.vector)
+    r = o.regs()
+    assert get_zmm(r) == zin and list(r.k) == list(regs.k) and list(r.gpr) == list(regs.gpr)
 
 
 # ---------------------------------------------------------------- the multi-instruction routines
@@ -290,6 +337,83 @@ def test_engine_runs_avx512x_programs(fast):
             fails.append((c["routine"], c["len"]) + bad)
         assert not fast or cnt.value > 0   # the VEX moves and the integer code took the fast loop's forms
     assert not fails, f"{len(fails)}/{len(PROGS['cases'])}, first: {fails[:4]}"
+
+
+def test_oracle_runs_avx512x_programs():
+    """The same 32 recorded routines through the oracle, to their int3: the
+    retired count, the GPRs and both destination areas."""
+    lay = PROGS["layout"]
+    buf_va = int(PROGS["buf_va"], 16)
+    assert len(PROGS["cases"]) == 32
+    fails = []
+    for c in PROGS["cases"]:
+        sp = program_space()
+        regs = regs_from_state(user_state(CODE_VA, 0, sp.cr3))
+        sp.write(buf_va + lay["src"], program_case(c, regs))
+        pfns, blob = sp.phys()
+        o = Oracle(pfns=pfns, blob=blob)
+        o.restore(regs)
+        o.set_limit(10 * c["icount"] + 1000)
+        ex = o.run()
+        if ex.status != EXIT_INT3:
+            fails.append((c["routine"], c["len"], "exit", ex.status, ex.vector, hex(ex.rip)))
+            continue
+        area = [o.read_virt(buf_va + lay[k], lay["area"]) for k in ("dst", "dst2")]
+        bad = program_check(c, o.icount(), list(o.regs().gpr), area[0], area[1])
+        if bad:
+            fails.append((c["routine"], c["len"]) + bad)
+    assert not fails, f"{len(fails)}/{len(PROGS['cases'])}, first: {fails[:4]}"
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["program-per-lane", "shared-programs"])
+@pytest.mark.parametrize("fast", [False, True], ids=["exec", "fast"])
+def test_engine_evex_code_matches_oracle_on_random_programs(fast, shared):
+    """The engine's host build against the oracle on random programs from the
+    EVEX pool (tests/progfuzz.py), VEX and legacy SSE forms between them, every
+    lane from its own zmm0-31 and k0-7: exit, rip, retired count, GPRs, RFLAGS,
+    zmm0-31, k0-7, MXCSR, the byte counter and the dirty set, per lane."""
+    from tests import progfuzz
+
+    L = sim_full()
+    n, seed = 192, 36
+    if shared:
+        sp, st, lanes = progfuzz.build_shared(n, 16, seed, sse=True, evex=True)
+    else:
+        sp, st, lanes = progfuzz.build(n, seed=seed, sse=True, evex=True)
+    kw = progfuzz.lane_state(n, seed, True, True)
+    want = progfuzz.oracle_run(sp, st, lanes, limit=2000, **kw)
+    pfns, blob = sp.phys()
+    arr = (C.c_uint64 * len(pfns))(*pfns)
+    bad = []
+    for i, ((va, g, flags), w) in enumerate(zip(lanes, want)):
+        regs = regs_from_state(st)
+        for k in range(16):
+            regs.gpr[k] = g[k]
+        progfuzz.set_lane_state(regs, i, **kw)
+        regs.rip, regs.rflags = va, flags
+        out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
+        L.sim_run_full(arr, blob, len(pfns), C.byref(regs), 2000, C.byref(out), 1 if fast else 0, C.byref(cnt), 0,
+                       C.byref(fin), None)
+        f = out.status == EXIT_FAULT
+        got = (out.status, out.vector if f else 0, out.error if f else 0, out.addr if f else 0, out.rip, out.icount)
+        f = w["status"] == EXIT_FAULT
+        exp = (w["status"], w["vector"] if f else 0, w["error"] if f else 0, w["addr"] if f else 0, w["rip"], w["icount"])
+        if got != exp:
+            bad.append((i, "exit", got, exp))
+        elif list(out.gpr) != w["gpr"] or out.rflags != w["rflags"]:
+            bad.append((i, "regs"))
+        elif get_zmm(fin) != w["zmm"]:
+            z = get_zmm(fin)
+            bad.append((i, "zmm", [(j // 8, j % 8, hex(z[j]), hex(w["zmm"][j])) for j in range(256) if z[j] != w["zmm"][j]][:3]))
+        elif list(fin.k) != w["k"] or out.mxcsr != w["mxcsr"]:
+            bad.append((i, "k/mxcsr", [hex(v) for v in fin.k], [hex(v) for v in w["k"]]))
+        elif out.nbytes != w["bytes"]:
+            bad.append((i, "bytes", out.nbytes, w["bytes"]))
+        elif {out.dirty[k] for k in range(min(out.ovn, 64))} != w["dirty"]:
+            bad.append((i, "dirty"))
+    assert all(w["status"] != EXIT_UNIMPLEMENTED for w in want)
+    assert sum(w["zmm"] != kw["zmm"][i] for i, w in enumerate(want)) > n // 2   # the EVEX forms ran
+    assert not bad, f"{len(bad)}/{n} lanes differ; first: {bad[:4]}"
 
 
 def test_vpabs_meets_its_minimum_in_a_selected_element():

@@ -19,8 +19,8 @@ import pytest
 from tests.golden.gen_native_vectors import splitmix_bytes
 from tests.golden.gen_sse_vectors import window_in
 from tests.oracle_lib import Oracle
-from tests.test_sse import BUF, layout, sim_lib, sim_run
-from wtf_amd.abi import EXIT_FAULT
+from tests.test_sse import BUF, SimResult, layout, sim_lib, sim_run
+from wtf_amd.abi import EXIT_FAULT, Regs
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 INT3 = 3
@@ -39,10 +39,28 @@ def run_both(L, sp, regs, win_va, limit=0):
     return slow, fast, cnt.value
 
 
-def same(a, b):
+def same(a, b, fa=None, fb=None):
+    """fa / fb: the two runs' final register files where the run returned them
+    (sim_run_full): zmm0-15's bits 511:256, zmm16-31 and k0-7 are compared too."""
+    full = fa is None or (bytes(fa.zmmh) == bytes(fb.zmmh) and bytes(fa.zmm_hi) == bytes(fb.zmm_hi) and
+                          list(fa.k) == list(fb.k) and fa.xcr0 == fb.xcr0)
     return (a.status == b.status and a.vector == b.vector and a.rip == b.rip and a.icount == b.icount and
             list(a.gpr) == list(b.gpr) and a.rflags == b.rflags and list(a.xmm) == list(b.xmm) and
-            list(a.ymmh) == list(b.ymmh) and a.nbytes == b.nbytes and bytes(a.win) == bytes(b.win))
+            list(a.ymmh) == list(b.ymmh) and a.nbytes == b.nbytes and bytes(a.win) == bytes(b.win) and full)
+
+
+def run_both_full(L, sp, regs, win_va, limit=0):
+    """run_both through sim_run_full: (slow, fast, fast-form count, slow's final registers, fast's)."""
+    pfns, blob = sp.phys()
+    arr = (C.c_uint64 * len(pfns))(*pfns)
+    res = []
+    cnt = C.c_uint64(0)
+    for fast in (0, 1):
+        out, fin = SimResult(), Regs()
+        L.sim_run_full(arr, blob, len(pfns), C.byref(regs), limit, C.byref(out), fast, C.byref(cnt), win_va,
+                       C.byref(fin), None)
+        res.append((out, fin))
+    return res[0][0], res[1][0], cnt.value, res[0][1], res[1][1]
 
 
 def test_integer_vectors_through_fast_forms():
@@ -214,6 +232,59 @@ def test_vector_moves_defer_to_generic_when_state_is_off():
         slow, fast, n = run_both(L, sp, regs, 0)
         assert (fast.status, fast.vector) == (EXIT_FAULT, vec), (code, kw, fast.status, fast.vector)
         assert same(slow, fast) and n == 0, (code, kw)
+
+
+def widening_program(vzu):
+    """A kernel stub that writes vector registers through VEX while XCR0 = 7,
+    then widens XCR0 to 0xe7 and stores zmm0 / 1 / 3 / 5 with vmovdqu64. A VEX
+    write zeroes the destination up to MAXVL (bits 511:128 / 511:256; SDM vol. 1
+    15.5) whatever XCR0 enables, so the stores show zeros there."""
+    from tests.golden.gen_avx512_vectors import evex
+
+    code = bytes.fromhex(
+        "0f05" "cccccccccccc"   # 0  syscall -> lstar = 8 (ring 0: xsetbv is privileged)
+        "c5fa6f0e"              # 8  vmovdqu xmm1, [rsi]    VEX.128 load
+        "c5fe6fda"              #    vmovdqu ymm3, ymm2     VEX.256 register move
+        + ("c5f877" if vzu else "") +  # vzeroupper
+        "b900000000" "b8e7000000" "ba00000000"  # mov ecx, 0; mov eax, 0xe7; mov edx, 0
+        "0f01d1")               #    xsetbv
+    for slot, reg in enumerate((0, 1, 3, 5)):
+        code += bytes(evex(1, 2, 1, 2, 0, 0, 0, reg, 0, 0x7F, mem=(7, None, 0, slot, 1)))  # vmovdqu64 [rdi + 64 * slot], zmm
+    return code
+
+
+@pytest.mark.parametrize("vzu", [False, True], ids=["moves", "moves-vzeroupper"])
+def test_vex_writes_zero_to_maxvl_before_xcr0_is_widened(vzu):
+    """Generic and fast give the same final registers and window, and both
+    equal the oracle: the fast loop's VEX forms zero bits 511:256 as ymm_put
+    does, not only while XCR0 enables the ZMM state."""
+    from tests.test_avx512 import get_zmm, sim_full
+    from tests.test_sse import CODE_VA
+
+    L = sim_full()
+    page = BUF & ~0xFFF
+    sp, regs = move_case(widening_program(vzu).hex(), 0x40, 0x100, xcr0=7)
+    regs.cr4 &= ~(3 << 20)  # no SMEP / SMAP: the stub runs on the test's user code page
+    regs.lstar = CODE_VA + 8
+    for k in range(16):
+        for h in range(4):
+            regs.zmmh[k][h] = 0xC0C0C0C0C0C0C0C0 + 16 * k + h
+    slow, fast, n, fs, ff = run_both_full(L, sp, regs, page + 0x100)
+    assert slow.status == INT3 and fast.status == INT3, (slow.status, slow.vector, fast.status, fast.vector)
+    assert n >= 2 + (1 if vzu else 0), n   # the VEX moves (and vzeroupper) ran as fast forms
+    pfns, blob = sp.phys()
+    o = Oracle(pfns=pfns, blob=blob)
+    o.restore(regs)
+    ex = o.run()
+    r = o.regs()
+    assert ex.status == INT3 and o.icount() == slow.icount == fast.icount
+    want = get_zmm(r)
+    assert want[8 * 1 + 2: 8 * 1 + 8] == [0] * 6 and want[8 * 3 + 4: 8 * 3 + 8] == [0] * 4   # zmm1 511:128, zmm3 511:256
+    assert (want[8 * 5 + 4] != 0) == (not vzu)    # zmm5: untouched unless vzeroupper ran
+    assert get_zmm(fs) == want and list(fs.k) == list(r.k), "generic != oracle"
+    assert get_zmm(ff) == want and list(ff.k) == list(r.k), "fast != oracle"
+    assert same(slow, fast, fs, ff)
+    assert o.read_virt(page + 0x100, 256) == bytes(slow.win[:256]) == bytes(fast.win[:256])
 
 
 def test_aligned_forms_fault_when_misaligned_on_fast_path():

@@ -7,8 +7,8 @@ runs program (i // 4) % 16, registers / flags / XMM state per lane), and the
 programs derive per-lane effective addresses from that state. Per lane, bit
 exact against the oracle: exit status / vector / error / address, rip, retired
 count, the 16 GPRs, RFLAGS, the coverage set, the dirty set, the byte counter,
-with sse the XMM / YMM-high / MXCSR state, and for every 8th lane the contents
-of the data window and the stack. tests/test_progfuzz_shared.py holds the
+with sse the XMM / YMM-high / MXCSR state, with evex zmm0-31 and k0-7 as well,
+and for every 8th lane the contents of the data window and the stack. tests/test_progfuzz_shared.py holds the
 generator to the divergence this needs.
 
 Which group hazards each test reaches (engine_run.h, k_run):
@@ -58,7 +58,8 @@ regroups, which brings the 32 lanes of a program side by side, and the
 programs that run into the instruction limit do so in lockstep; both push the
 figure far above the 4 lanes of a program that a wave holds in lane order.
 Stops of a fresh lane in one group with a resumed (skip) lane, fixed order:
-668 (seed 31) and 670 (seed 34). The 61 tests of the module take 19 s.
+668 (seed 31) and 670 (seed 34). The 61 tests of the module before the
+evex case took 19 s; with it and the reduced rep stos case there are 76.
 """
 import numpy as np
 import pytest
@@ -70,23 +71,22 @@ pytestmark = pytest.mark.gpu
 
 N, N_PROGRAMS, LIMIT = 512, 16, 2000
 CASES = progfuzz.SHARED_CASES
-INT_A, INT_B, SSE, FP = CASES
+INT_A, INT_B, SSE, FP, EVEX = CASES
 MORE = ((progfuzz.WIN2_VA, progfuzz.WIN2_LEN),)
 
 
 def case_id(c):
-    return f"seed{c[0]}" + ("-sse" if c[1] else "") + ("-fp" if c[2] else "")
+    return f"seed{c[0]}" + ("-sse" if c[1] else "") + ("-fp" if c[2] else "") + ("-evex" if c[3] else "")
 
 
 class Workload:
     def __init__(self, case):
-        seed, sse, fp = case
+        seed, sse, fp, evex = case
         self.case = case
-        self.sp, self.st, self.lanes, self.progs = progfuzz.build_shared_info(N, N_PROGRAMS, seed, sse=sse, fp=fp)
-        self.kw = {}
-        if sse:
-            self.kw = dict(xmm=progfuzz.lane_xmm(N, seed), ymmh=progfuzz.lane_xmm(N, seed, 0x4E4),
-                           mxcsr=progfuzz.lane_mxcsr(N, seed))
+        self.evex = evex
+        self.sp, self.st, self.lanes, self.progs = progfuzz.build_shared_info(N, N_PROGRAMS, seed, sse=sse, fp=fp,
+                                                                              evex=evex)
+        self.kw = progfuzz.lane_state(N, seed, sse, evex)
         self.want = progfuzz.oracle_run(self.sp, self.st, self.lanes, limit=LIMIT, more=MORE, **self.kw)
         self._bp = None
 
@@ -158,11 +158,7 @@ def load_lanes(eng, w):
         for k in range(16):
             r.gpr[k] = g[k]
         r.rip, r.rflags = va, flags
-        if w.kw:
-            for k in range(16):
-                r.xmm[k][0], r.xmm[k][1] = w.kw["xmm"][i][2 * k], w.kw["xmm"][i][2 * k + 1]
-                r.ymmh[k][0], r.ymmh[k][1] = w.kw["ymmh"][i][2 * k], w.kw["ymmh"][i][2 * k + 1]
-            r.mxcsr = w.kw["mxcsr"][i]
+        progfuzz.set_lane_state(r, i, **w.kw)
     eng.write_regs(regs)
 
 
@@ -220,6 +216,12 @@ def differences(eng, w, want, cov=True):
             bad.append((i, prog, "xmm/mxcsr"))
         elif w.kw and [r.ymmh[k][h] for k in range(16) for h in range(2)] != x["ymmh"]:
             bad.append((i, prog, "ymmh"))
+        elif w.evex and progfuzz.get_zmm(r) != x["zmm"]:
+            z = progfuzz.get_zmm(r)
+            bad.append((i, prog, "zmm (register, qword, got, expected)",
+                        [(j // 8, j % 8, hex(z[j]), hex(x["zmm"][j])) for j in range(256) if z[j] != x["zmm"][j]][:4]))
+        elif w.evex and [r.k[j] for j in range(8)] != x["k"]:
+            bad.append((i, prog, "k", [hex(r.k[j]) for j in range(8)], [hex(v) for v in x["k"]]))
         elif cov and covs.get(i, set()) != x["cov"]:
             bad.append((i, prog, "cov", sorted(hex(v) for v in covs.get(i, set()) ^ x["cov"])[:8]))
         elif set(eng.dirty(i)) != x["dirty"]:
@@ -451,7 +453,7 @@ def test_slice_length_is_path_independent(case, variant, workloads, monkeypatch)
 # 5. breakpoints, resume and mixed skip groups
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("regroup", [False, True], ids=["fixed-order", "regroup-64"])
-@pytest.mark.parametrize("case", [INT_A, FP], ids=case_id)
+@pytest.mark.parametrize("case", [INT_A, FP, EVEX], ids=case_id)
 def test_breakpoints_with_mixed_skip_groups(case, regroup, workloads, monkeypatch):
     w = workloads(case)
     want = w.want_bp()
@@ -505,4 +507,71 @@ def test_breakpoints_with_mixed_skip_groups(case, regroup, workloads, monkeypatc
     if not regroup:
         print(f"{case_id(case)}: {mixed} stops in a group with a skip lane")
         assert mixed > 0
+    eng.close()
+
+
+# ---------------------------------------------------------------------------
+# 6. the finding of the evex case, reduced
+# ---------------------------------------------------------------------------
+def test_rep_stos_first_write_across_a_page_in_part_of_a_group():
+    """rep stosq, 5 qwords, the first across a page edge, on the 64 lanes of one
+    wave at one rip. Of every four lanes, two have written the first page only
+    (the second page's copy-on-write sends them round the slow step's retry),
+    one has written both (it finishes in its first attempt) and one crosses
+    into the read-only page (#PF, nothing written). The evex case met this in
+    program 10 and the retrying lanes lost their first qword (engine_ops.h,
+    string_op). Every lane against the oracle, the window's bytes included."""
+    from wtf_amd.engine import Engine
+    from wtf_amd.tools.snapshot import AddressSpace, user_state
+
+    n = 64
+    code = bytes.fromhex("8803" "8802" "f348ab" "cc")  # mov [rbx], al; mov [rdx], al; rep stosq; int3
+    sp = AddressSpace()
+    sp.map_range(progfuzz.CODE_VA, code + b"\xcc" * (0x1000 - len(code)), write=False)
+    sp.map_range(progfuzz.WIN_VA, bytes((7 * i + 1) & 0xFF for i in range(0x2000)), nx=True)
+    sp.map(progfuzz.RO_VA, bytes(0x1000), write=False, nx=True)
+    sp.map_range(progfuzz.STACK_VA, bytes(0x2000), nx=True)
+    st = user_state(progfuzz.CODE_VA, progfuzz.STACK_TOP, sp.cr3)
+    lanes = []
+    for i in range(n):
+        g = [0x0101010101010101 * (i + 1)] * 16
+        g[4] = progfuzz.STACK_TOP
+        g[1] = 5                                   # rcx
+        g[3] = progfuzz.WIN_VA + 0x10 + i          # rbx: the first page
+        g[2] = progfuzz.WIN_VA + (0x1010 if i % 4 == 3 else 0x20) + i   # rdx: the second page for every fourth lane
+        g[7] = progfuzz.WIN_VA + (0x1FFC if i % 4 == 0 else 0xFFC)      # rdi: into the read-only page / across RW|RW
+        lanes.append((progfuzz.CODE_VA, g, 0x202))
+    want = progfuzz.oracle_run(sp, st, lanes, limit=LIMIT)
+    assert {w["status"] for w in want} == {EXIT_FAULT, 3}
+    eng = Engine(0)
+    pfns, blob = sp.phys()
+    eng.load_pool(pfns, blob)
+    eng.alloc_lanes(n, overlay_pages=16, cov_entries=64)
+    eng.set_initial_state(regs_from_state(st))
+    eng.set_limit(LIMIT)
+    eng.restore()
+    regs = eng.read_regs(0, n)
+    for i, (va, g, flags) in enumerate(lanes):
+        for k in range(16):
+            regs[i].gpr[k] = g[k]
+        regs[i].rip, regs[i].rflags = va, flags
+    eng.write_regs(regs)
+    eng.run()
+    ex = eng.exits()
+    out = eng.read_regs(0, n)
+    bad = []
+    for i, x in enumerate(want):
+        e, r = ex[i], out[i]
+        f = x["status"] == EXIT_FAULT
+        if (e.status, r.rip, e.icount) != (x["status"], x["rip"], x["icount"]) or \
+                (f and (e.vector, e.error, e.addr) != (x["vector"], x["error"], x["addr"])):
+            bad.append((i, "exit", e.status, hex(r.rip), e.icount))
+        elif [r.gpr[k] for k in range(16)] != x["gpr"]:
+            bad.append((i, "regs"))
+        elif set(eng.dirty(i)) != x["dirty"]:
+            bad.append((i, "dirty"))
+        elif eng.read_virt(i, progfuzz.WIN_VA, 0x2000) != x["win"]:
+            got = eng.read_virt(i, progfuzz.WIN_VA, 0x2000)
+            bad.append((i, "memory", [j for j in range(0x2000) if got[j] != x["win"][j]][:10]))
+    assert not bad, f"{len(bad)}/{n} lanes differ; first: {bad[:4]}"
     eng.close()

@@ -564,3 +564,69 @@ def test_gpu_matches_native_avx512_vectors():
                 fails.append((c["name"], c["code"]) + bad)
     assert total == len(DOC["cases"])
     assert not fails, f"{len(fails)}/{total} mismatches, first: {fails[:6]}"
+
+
+@pytest.mark.parametrize("vzu", [False, True], ids=["moves", "moves-vzeroupper"])
+def test_gpu_vex_writes_zero_to_maxvl_before_xcr0_is_widened(vzu):
+    """tests/test_fast_path.py's widening program on the 64 lanes of one wave:
+    XCR0 = 7 and nonzero zmm0-15 uppers, a VEX.128 load, a VEX.256 register
+    move (and vzeroupper), xsetbv to 0xe7, vmovdqu64 stores. The odd lanes'
+    load crosses a page, which takes them to the generic step for that VEX
+    write while the even lanes stay in the fast loop. Every lane against the
+    oracle: exit, GPRs, zmm0-31, k0-7, XCR0 and the stored bytes."""
+    from tests.test_avx512 import get_zmm
+    from tests.test_fast_path import move_case, widening_program
+    from tests.test_sse import CODE_VA as CVA
+    from wtf_amd.engine import Engine
+
+    n = 64
+    page = BUF & ~0xFFF
+    sp, init = move_case(widening_program(vzu).hex(), 0x40, 0x100, xcr0=7)
+    init.cr4 &= ~(3 << 20)  # no SMEP / SMAP: the stub runs on the test's user code page
+    init.lstar = CVA + 8
+    for k in range(16):
+        for h in range(4):
+            init.zmmh[k][h] = 0xC0C0C0C0C0C0C0C0 + 16 * k + h
+    srcs = (page + 0x40, page + 0x1000 - 8)   # even lanes: inside the page; odd lanes: across its end
+    pfns, blob = sp.phys()
+    want = []
+    for src in srcs:
+        o = Oracle(pfns=pfns, blob=blob)
+        init.gpr[6] = src
+        o.restore(init)
+        ex = o.run()
+        assert ex.status == EXIT_INT3
+        r = o.regs()
+        z = get_zmm(r)
+        assert z[8 * 1 + 2: 8 * 1 + 8] == [0] * 6 and z[8 * 3 + 4: 8 * 3 + 8] == [0] * 4
+        want.append((o.icount(), list(r.gpr), z, list(r.k), r.xcr0, o.read_virt(page + 0x100, 256)))
+    eng = Engine(0)
+    eng.load_pool(pfns, blob)
+    eng.alloc_lanes(n, overlay_pages=4, cov_entries=64)
+    eng.set_initial_state(init)
+    eng.set_limit(0)
+    eng.restore()
+    regs = eng.read_regs(0, n)
+    for i in range(n):
+        regs[i].gpr[6] = srcs[i & 1]
+    eng.write_regs(regs)
+    eng.run()
+    ex = eng.exits()
+    out = eng.read_regs(0, n)
+    bad = []
+    for i in range(n):
+        icount, gpr, z, kk, xcr0, mem = want[i & 1]
+        r, e = out[i], ex[i]
+        if (e.status, e.icount) != (EXIT_INT3, icount):
+            bad.append((i, "exit", e.status, e.vector, e.icount))
+        elif list(r.gpr) != gpr or r.xcr0 != xcr0:
+            bad.append((i, "regs"))
+        elif get_zmm(r) != z:
+            g = get_zmm(r)
+            bad.append((i, "zmm", [(j // 8, j % 8, hex(g[j]), hex(z[j])) for j in range(256) if g[j] != z[j]][:4]))
+        elif list(r.k) != kk:
+            bad.append((i, "k"))
+        elif eng.read_virt(i, page + 0x100, 256) != mem:
+            bad.append((i, "memory"))
+    assert not bad, f"{len(bad)}/{n} lanes differ; first: {bad[:4]}"
+    eng.close()

@@ -966,9 +966,38 @@ __device__ __forceinline__ bool muldiv(const Lane &L, u32 sub, u32 sz, u64 src, 
 }
 
 // ---------------------------------------------------------------- string ops
-__device__ __forceinline__ int string_op(const Dev &P, Lane &L, const UOp &u) {
+// A value the compiler must treat as per-lane (a VGPR), although every lane
+// holds the same. The engine is built with -structurizecfg-skip-uniform-regions
+// (Makefile), which leaves branches on wave-uniform values as scalar branches;
+// string_op's loop mixes such branches (the UOp's fields) with per-lane exits
+// (a miss, a fault, rcx = 0) and is entered again, by a part of the group, from
+// exec_retry's attempts. On MI355X that build lost a lane's first iteration:
+// rep stosq whose first element crosses into a page the lane had not written
+// yet (its copy-on-write sends the lane round exec_retry), in a group where
+// other lanes finished or faulted in their first attempt; rdi / rcx moved on,
+// the 8 bytes were never stored (tests/test_gpu_progfuzz_shared.py, the evex
+// case; the same source built without the flag stored them). With the fields
+// below per-lane, the loop's control flow is structurized like any other
+// divergent code.
+#ifdef WTFGPU_HOST_SIM
+#define WTFGPU_PER_LANE(x) \
+  do {                     \
+  } while (0)
+#else
+#define WTFGPU_PER_LANE(x) asm volatile("" : "+v"(x))
+#endif
+__device__ __forceinline__ int string_op(const Dev &P, Lane &L, const UOp &uu) {
   // a4 movs, a6 cmps, aa stos, ac lods, ae scas; 6c ins, 6e outs (U31: all
   // ones in, nothing out, #GP(0) at CPL > IOPL checked per iteration)
+  struct {
+    u32 sub, asz, p67, rep, seg, rex;
+  } u = {uu.sub, uu.asz, uu.p67, uu.rep, uu.seg, uu.rex};
+  WTFGPU_PER_LANE(u.sub);
+  WTFGPU_PER_LANE(u.asz);
+  WTFGPU_PER_LANE(u.p67);
+  WTFGPU_PER_LANE(u.rep);
+  WTFGPU_PER_LANE(u.seg);
+  WTFGPU_PER_LANE(u.rex);
   const bool io = u.sub & 0x10;
   const u32 op = io ? (0x60 | (u.sub & 0xe)) : (0xa0 | (u.sub & 0xe));
   const u32 sz = io && u.asz == 8 ? 4 : u.asz;
