@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <vector>
 #include "../../wtf_amd/csrc/engine_fast.h"
+#include "../../wtf_amd/csrc/engine_ptmark.h"
 using namespace wtfgpu_dev;
 
 // Tenet stream of the next sim_run_full (sim_set_tenet; engine_exec.h TenetDev)
@@ -45,7 +46,11 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
   memcpy(pool + 4096, pages, npages * 4096);
   std::vector<uint32_t> map(maxpfn + 1, 0);
   for (uint64_t i = 0; i < npages; i++) if (!map[gpfns[i]]) map[gpfns[i]] = (uint32_t)(i + 1);
-  std::vector<uint32_t> ptbits((maxpfn + 32) / 32, 0);
+  // the engine's own marking of page-table pages (wtfgpu_set_initial_state)
+  const std::vector<uint32_t> ptbits = wtfgpu_host::mark_pt_bits(r0->cr3, map.size(), [&](uint64_t gpfn) {
+    const uint32_t idx = gpfn < map.size() ? map[gpfn] : 0;
+    return idx ? (const uint8_t *)pool + (uint64_t)idx * 4096 : nullptr;
+  });
   const uint32_t K = 64;
   uint8_t *ov = (uint8_t *)aligned_alloc(4096, K * 4096);
   std::vector<uint32_t> ovg(K), ovc(1);
@@ -271,6 +276,33 @@ int sim_digest(const uint8_t *bytes, uint32_t avail, uint32_t *out) {
                           d.asz, d.bsz, d.asrc, d.bsrc, d.is_mem, d.supported};
   memcpy(out, v, sizeof(v));
   return dr;
+}
+// The device walk alone over a snapshot's pages, as a ring-0 read (so only the
+// present bits decide, and whether the address is canonical): 0 and *gpa, or -1.
+int sim_translate(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, uint64_t cr3, uint64_t va,
+                  uint64_t *gpa) {
+  uint64_t maxpfn = 0;
+  for (uint64_t i = 0; i < npages; i++) maxpfn = gpfns[i] > maxpfn ? gpfns[i] : maxpfn;
+  uint8_t *pool = (uint8_t *)aligned_alloc(4096, (npages + 1) * 4096);
+  memset(pool, 0, 4096);
+  memcpy(pool + 4096, pages, npages * 4096);
+  std::vector<uint32_t> map(maxpfn + 1, 0), ptbits((maxpfn + 32) / 32, 0);
+  for (uint64_t i = 0; i < npages; i++) if (!map[gpfns[i]]) map[gpfns[i]] = (uint32_t)(i + 1);
+  Dev P{};
+  P.pool = pool;
+  P.pfn_map = map.data();
+  P.pfn_map_len = map.size();
+  P.ptbits = ptbits.data();
+  P.nlanes = 1;
+  P.K = 1;
+  Lane L{};
+  L.cr3 = cr3;
+  tlb_flush(L);
+  uint64_t td, gpfn;
+  const bool ok = walk<false>(P, L, va, ACC_R, td, gpfn);
+  if (ok) *gpa = gpfn << 12 | (va & 0xfff);
+  free(pool);
+  return ok ? 0 : -1;
 }
 int sim_run_mode(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, const wtfgpu_regs_t *r0,
                  uint64_t limit, SimResult *out, int fast, uint64_t *fast_count, uint64_t win_va) {

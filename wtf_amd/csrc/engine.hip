@@ -22,6 +22,7 @@
 
 #include "engine_run.h"
 #include "engine_kernels.h"
+#include "engine_ptmark.h"
 
 using namespace wtfgpu_dev;
 
@@ -796,31 +797,11 @@ static int mark_pt_pages(wtfgpu_ctx *c) {
   if (!c->d_ptbits) return WTFGPU_OK;
   const u64 maplen = c->h_map.size();
   if (maplen == 0) return WTFGPU_OK;
-  std::vector<u32> bits((maplen + 31) / 32, 0);
   auto page = [&](u64 gpfn) -> const u8 * {
     const u32 idx = gpfn < maplen ? c->h_map[gpfn] : 0;
     return idx ? c->h_pool.data() + (u64)(idx - 1) * WTFGPU_PAGE_SIZE : nullptr;
   };
-  auto mark = [&](u64 gpfn) {
-    if (gpfn < maplen) bits[gpfn >> 5] |= 1u << (gpfn & 31);
-  };
-  std::vector<std::pair<u64, int>> work;
-  work.push_back({c->initial.cr3 >> 12 & 0xffffffffffull, 3});
-  while (!work.empty()) {
-    auto [pfn, level] = work.back();
-    work.pop_back();
-    if (pfn < maplen && (bits[pfn >> 5] >> (pfn & 31)) & 1) continue;
-    mark(pfn);
-    const u8 *pg = page(pfn);
-    if (!pg || level == 0) continue;
-    for (int i = 0; i < 512; i++) {
-      u64 e;
-      memcpy(&e, pg + 8 * i, 8);
-      if (!(e & 1)) continue;
-      if ((level == 1 || level == 2) && (e & 0x80)) continue;  // large leaf
-      work.push_back({(e & 0x000ffffffffff000ull) >> 12, level - 1});
-    }
-  }
+  const std::vector<u32> bits = wtfgpu_host::mark_pt_bits(c->initial.cr3, maplen, page);  // engine_ptmark.h
   HIPCHK(hipMemcpyAsync(c->d_ptbits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, c->q->stream));
   HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
