@@ -228,7 +228,7 @@ def bcd_range_f80(rng):
 def run_oracle(c, buf_va):
     """One case through the oracle: (status, vector, fcw, fsw, ftw, st, fl, mem)."""
     from tests.oracle_lib import Oracle
-    from tests.test_sse import layout
+    from tests.insn_cases import layout
     sp, regs = layout(bytes.fromhex(c["code"]), buf_va, bytes.fromhex(c["mem"]).ljust(256, b"\0"))
     regs.gpr[6] = buf_va
     case_regs(c, regs)
@@ -243,7 +243,7 @@ def run_oracle(c, buf_va):
 
 
 def main():
-    from tests.test_sse import BUF
+    from tests.insn_cases import BUF
     cases = make_cases()
     doc = {"buf_va": hex(BUF), "cases": []}
     for c in cases:

@@ -312,4 +312,5 @@ int sim_run(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, const 
             uint64_t limit, SimResult *out) {
   return sim_run_mode(gpfns, pages, npages, r0, limit, out, 0, nullptr, 0);
 }
+uint64_t sim_result_size() { return sizeof(SimResult); }
 }

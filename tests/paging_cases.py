@@ -592,3 +592,47 @@ def own_or_table(pfn):
 
 
 FAMILIES = {"translation": 87, "rights": 158, "alias": 30, "edit": 69, "link": 1, "link-unasserted": 1, "host": 1}
+
+
+# ---------------------------------------------------------------- shared by the CPU and the GPU tests
+ASSERTED = [c for c in cases() if c.family != "link-unasserted"]
+
+
+def diff(got, want):
+    """The fields in which an engine's result differs from the model's."""
+    bad = []
+    if got["status"] != want.status:
+        bad.append(("status", got["status"], want.status))
+    elif want.status == EXIT_FAULT:
+        if (got["vector"], got["error"]) != (want.vector, want.error):
+            bad.append(("fault", got["vector"], got["error"], want.vector, want.error))
+        if want.addr is not None and got["addr"] != want.addr:
+            bad.append(("addr", hex(got["addr"]), hex(want.addr)))
+    for k in ("rip", "icount"):
+        if got[k] != getattr(want, k):
+            bad.append((k, got[k], getattr(want, k)))
+    bad += [("gpr", r, hex(got["gpr"][r]), hex(v)) for r, v in want.gpr.items() if got["gpr"][r] != v]
+    bad += [("vec", i) for i, b in want.vec.items() if got["vec"][i][:len(b)] != b]
+    if got["dirty"] != want.dirty:
+        bad.append(("dirty", [hex(p) for p in got["dirty"]], [hex(p) for p in want.dirty]))
+    elif got["mem"] != want.mem:
+        bad.append(("mem", [hex(p) for p in want.dirty if got["mem"][p] != want.mem[p]]))
+    for va, b in got["views"].items():
+        # (the host build's window is the guest's walk from ring 0, byte by byte: compared where all 8 bytes translate)
+        if b != want.views[va] and not ("fast" in got and (want.views[va] is None or not M.canonical(va))):
+            bad.append(("view", hex(va), b, want.views[va]))
+    return bad
+
+
+def host_addresses():
+    vas = {va for c in cases() for _, va, _ in c.ops}
+    vas |= {U1G + GIB - 1, L2 + MIB2 - 1, L2 + MIB2, HOLE, HOLE - 1, L2_U0, L2_NX + 0x1234, L2_W0 + 7,
+            U1G_U0 + 0x2FFFFFFF, PTWIN, LWIN + 0x1FFFFF, KLEAF + 0x3000, KLINK, 0, 0xFFFF800000000000}
+    return sorted(vas)
+
+
+HOST_WRITES = [  # (name, va, bytes written, lands)
+    ("ro-2m-leaf", L2_W0 + 0x1FFC, 8, True), ("ro-1g-leaf", U1G_W0 + GIB - 8, 8, True),
+    ("supervisor-nx-4k", PLACE["U0", 1] + 0xFF0, 16, True), ("absent-frame", L2 + MIB2 // 2 + 4, 8, True),
+    ("out-of-leaf-into-hole", L2_B + MIB2 - 4, 8, False), ("hole", HOLE + 8, 8, False),
+]

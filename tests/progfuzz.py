@@ -652,3 +652,26 @@ def oracle_run(sp: AddressSpace, st: dict, lanes, limit=20000, breakpoints=(), x
 # runs them on the engine.
 SHARED_CASES = [(31, False, False, False), (32, False, False, False), (35, True, False, False), (34, True, True, False),
                 (36, True, False, True)]
+
+
+def run_gpu(sp, st, lanes, limit=20000, overlay_pages=8):
+    """The lanes of build() through k_run: (the engine, run()'s statistics)."""
+    import numpy as np
+    from wtf_amd.engine import Engine
+
+    n = len(lanes)
+    eng = Engine(0)
+    pfns, blob = sp.phys()
+    eng.load_pool(pfns, blob)
+    eng.alloc_lanes(n, overlay_pages=overlay_pages, cov_entries=4096)
+    eng.set_initial_state(regs_from_state(st))
+    eng.set_limit(limit)
+    eng.restore()
+    g = eng.read_gprs()
+    for i, (va, regs, flags) in enumerate(lanes):
+        g[i, :16] = np.array(regs, dtype=np.uint64)
+        g[i, 16] = va
+        g[i, 17] = flags
+    eng.write_gprs(g)
+    stats = eng.run()
+    return eng, stats

@@ -459,3 +459,26 @@ def lane_view(status, vector, error, addr, icount, nbytes, r, pages: dict) -> di
         "fpst": list(r.fpst), "xmm": [int(x) for row in r.xmm for x in row],
         "ymmh": [int(x) for row in r.ymmh for x in row], "pages": pages,
     }
+
+
+def sim_lanes(sp, st, ln, limit=3000):
+    """Each lane through the engine's host build (tests/simlane.py, fast loop first): lane_view per lane."""
+    from tests import simlane
+
+    img = simlane.image(sp)
+    out = []
+    for va, g, flags in ln:
+        r = regs_from_state(st)
+        for k in range(16):
+            r.gpr[k] = g[k]
+        r.rip, r.rflags = va, flags
+        pages = simlane.page_buffer()
+        res, fin, _ = simlane.run(img, r, limit=limit, fast=True, pages=pages)
+        out.append(lane_view(res.status, res.vector, res.error, res.addr, res.icount, res.nbytes, fin,
+                             simlane.dirty_pages(res, pages)))
+    return out
+
+
+def diff(a: dict, b: dict):
+    """The keys in which two lane views differ."""
+    return [k for k in a if a[k] != b[k]]

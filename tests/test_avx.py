@@ -6,99 +6,25 @@ sim_lane.cc) against native-execution vectors (tests/golden/gen_avx_vectors.py:
 then the #UD / #NM / #GP rules native execution cannot show. The GPU runs the
 same vectors in tests/test_gpu_sse.py.
 """
-import gzip
-import json
-import os
-
 import pytest
 
-from tests.golden.gen_native_vectors import splitmix_bytes
-from tests.test_sse import BUF, layout, sim_lib, sim_run
-from tests.oracle_lib import Oracle
+from tests import simlane
+from tests.insn_cases import BUF, layout, oracle_of
+from tests.vector_replay import AVX, replay_oracle, replay_sim, run_family
 from wtf_amd.abi import EXIT_FAULT, EXIT_TIMEOUT, EXIT_UNIMPLEMENTED, RUNNING
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CODE_VA = 0x140001000
-
-
-def load():
-    with gzip.open(os.path.join(HERE, "golden", "avx_vectors.json.gz"), "rt") as f:
-        return json.load(f)
-
-
-DOC = load()
-
-
-def set_ymm(regs, ys):
-    for i in range(16):
-        regs.xmm[i][0], regs.xmm[i][1] = ys[4 * i], ys[4 * i + 1]
-        regs.ymmh[i][0], regs.ymmh[i][1] = ys[4 * i + 2], ys[4 * i + 3]
-
-
-def get_ymm(xmm, ymmh):
-    """32 + 32 u64 (xmm / ymmh, reg-major) -> 64 u64 in native ymm order."""
-    out = []
-    for i in range(16):
-        out += [xmm[2 * i], xmm[2 * i + 1], ymmh[2 * i], ymmh[2 * i + 1]]
-    return out
-
-
-def case_regs(c, regs):
-    for i in range(16):
-        regs.gpr[i] = int(c["in"][i], 16)
-    regs.rflags = int(c["fl"], 16) | 0x200
-    set_ymm(regs, [int(v, 16) for v in c["yin"]])
-    return regs
-
-
-def window(c):
-    return splitmix_bytes(int(c["seed"], 16), 256)
+DOC = AVX.doc
 
 
 @pytest.mark.parametrize("chunk", range(4))
 def test_oracle_matches_native_avx(chunk):
-    buf_va = int(DOC["buf_va"], 16)
-    fails = []
     cases = DOC["cases"][chunk::4]
-    for c in cases:
-        sp, regs = layout(bytes.fromhex(c["code"]), buf_va, window(c))
-        pfns, blob = sp.phys()
-        o = Oracle(pfns=pfns, blob=blob)
-        o.restore(case_regs(c, regs))
-        ex = o.step()
-        if ex.status != RUNNING:
-            fails.append((c["name"], c["code"], "exit", ex.status, ex.vector))
-            continue
-        r = o.regs()
-        if list(r.gpr) != [int(x, 16) for x in c["out"]] or (r.rflags ^ int(c["flo"], 16)) & 0x8D5:
-            fails.append((c["name"], c["code"], "regs"))
-            continue
-        got = get_ymm([r.xmm[i][h] for i in range(16) for h in range(2)],
-                      [r.ymmh[i][h] for i in range(16) for h in range(2)])
-        if got != [int(v, 16) for v in c["yout"]]:
-            fails.append((c["name"], c["code"], "ymm"))
-            continue
-        win = bytearray(window(c))
-        for i, v in c["diff"]:
-            win[i] = v
-        if o.read_virt(buf_va, 256) != bytes(win):
-            fails.append((c["name"], c["code"], "mem"))
+    fails = run_family(AVX, replay_oracle, cases)
     assert not fails, f"{len(fails)}/{len(cases)} mismatches, first: {fails[:6]}"
 
 
 def test_engine_avx_code_matches_native_vectors():
-    L = sim_lib()
-    buf_va = int(DOC["buf_va"], 16)
-    fails = []
-    for c in DOC["cases"]:
-        sp, regs = layout(bytes.fromhex(c["code"]), buf_va, window(c))
-        out = sim_run(L, sp, case_regs(c, regs))
-        if out.status != 3 or out.icount != 1:
-            fails.append((c["name"], c["code"], "exit", out.status, out.vector))
-        elif list(out.gpr) != [int(x, 16) for x in c["out"]] or (out.rflags ^ int(c["flo"], 16)) & 0x8D5:
-            fails.append((c["name"], c["code"], "regs"))
-        elif get_ymm(list(out.xmm), list(out.ymmh)) != [int(v, 16) for v in c["yout"]]:
-            fails.append((c["name"], c["code"], "ymm"))
+    fails = run_family(AVX, replay_sim, DOC["cases"])
     assert not fails, f"{len(fails)}/{len(DOC['cases'])} mismatches, first: {fails[:6]}"
 
 
@@ -174,24 +100,21 @@ AVX_FAULT_CASES = [
 ]
 
 
-def run1(code, cr0=None, cr4=None, xcr0=None, L=None):
+def run1(code, cr0=None, cr4=None, xcr0=None, sim=False):
     sp, regs = layout(bytes(code), BUF, bytes(range(256)), cr0=cr0, cr4=cr4)
     regs.gpr[3] = BUF + 0x10  # rbx: 16-aligned, not 32-aligned (BUF is 0x...800)
     regs.gpr[6] = BUF + 0x13
     if xcr0 is not None:
         regs.xcr0 = xcr0
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    o = oracle_of(sp)
     o.restore(regs)
     ex = o.step()
-    sim = sim_run(L, sp, regs) if L is not None else None
-    return ex, sim
+    return ex, simlane.run(sp, regs)[0] if sim else None
 
 
 @pytest.mark.parametrize("code,status,vector", AVX_FAULT_CASES)
 def test_avx_faults_oracle_and_engine(code, status, vector):
-    L = sim_lib()
-    ex, sim = run1(code, L=L)
+    ex, sim = run1(code, sim=True)
     assert ex.status == status, (bytes(code).hex(), ex.status, ex.vector)
     if vector is not None:
         assert ex.vector == vector
@@ -200,13 +123,12 @@ def test_avx_faults_oracle_and_engine(code, status, vector):
 
 
 def test_avx_state_gating():
-    L = sim_lib()
     vpxor = [0xC5, 0xF5, 0xEF, 0xC2]
     for kw, vec in ((dict(cr4=0x370678 & ~0x40000), 6), (dict(xcr0=0x3), 6), (dict(cr0=0x80050031 | 8), 7)):
-        ex, sim = run1(vpxor, L=L, **kw)
+        ex, sim = run1(vpxor, sim=True, **kw)
         assert (ex.status, ex.vector) == (EXIT_FAULT, vec), kw
         assert (sim.status, sim.vector) == (EXIT_FAULT, vec), kw
-    ex, sim = run1(vpxor, L=L, cr0=0x80050031 | 4)  # CR0.EM does not gate VEX
+    ex, sim = run1(vpxor, sim=True, cr0=0x80050031 | 4)  # CR0.EM does not gate VEX
     assert ex.status == RUNNING and sim.status == 3
 
 
@@ -217,8 +139,7 @@ def test_vzeroupper_keeps_low_halves_and_legacy_keeps_high():
     for i in range(16):
         regs.xmm[i][0], regs.xmm[i][1] = i + 1, i + 2
         regs.ymmh[i][0], regs.ymmh[i][1] = 100 + i, 200 + i
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    o = oracle_of(sp)
     o.restore(regs)
     assert o.step().status == RUNNING
     r = o.regs()
@@ -231,7 +152,6 @@ def test_encoding_space_oracle_equals_engine():
     legacy 0f 38 / 0f 3a maps (each mandatory prefix): the oracle and the
     engine's decode agree on #UD / UNIMPLEMENTED / executed for every opcode,
     register and memory ModRM forms alike."""
-    L = sim_lib()
     codes = []
     for modrm in (0xC1, 0x06):
         for m in range(5):
@@ -246,13 +166,12 @@ def test_encoding_space_oracle_equals_engine():
     for code in codes:
         sp, regs = layout(bytes(code), BUF, bytes(range(256)))
         regs.gpr[3], regs.gpr[6] = BUF + 0x10, BUF + 0x13
-        pfns, blob = sp.phys()
-        o = Oracle(pfns=pfns, blob=blob)
+        o = oracle_of(sp)
         o.restore(regs)
         ex = o.step()
         if ex.status == RUNNING:  # the limit stops the lane after its second instruction
             ex = o.step()
-        sim = sim_run(L, sp, regs, limit=1)
+        sim = simlane.run(sp, regs, limit=1)[0]
         want = (EXIT_TIMEOUT, 3) if ex.status == RUNNING else (ex.status,)
         if sim.status not in want or (ex.status == EXIT_FAULT and sim.vector != ex.vector):
             bad.append((bytes(code).hex(), ex.status, ex.vector, sim.status, sim.vector))

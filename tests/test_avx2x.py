@@ -10,58 +10,19 @@ the GPU runs them in tests/test_gpu_sse.py. Hand-checked: the #UD rules, the
 CPUID bits, and a gather whose element faults (the earlier elements stay
 done, engine and oracle alike).
 """
-import gzip
-import json
-import os
-
 import pytest
 
-from tests.golden.gen_avx2x_vectors import case_inputs
-from tests.oracle_lib import Oracle
-from tests.test_avx import get_ymm, set_ymm
-from tests.test_fp import check
-from tests.test_sse import layout, sim_lib, sim_run
-
+from tests import simlane
+from tests.insn_cases import get_ymm, layout, oracle_of, set_ymm
+from tests.vector_replay import AVX2X, replay_oracle, replay_sim, run_family
 from wtf_amd.abi import EXIT_FAULT
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def load():
-    with gzip.open(os.path.join(HERE, "golden", "avx2x_vectors.json.gz"), "rt") as f:
-        return json.load(f)
-
-
-DOC = load()
-
-
-def inputs(c):
-    ymm, win = case_inputs(int(c["seed"], 16), c["ew"], c["kind"])
-    for i, v in c.get("yset", []):
-        ymm[i // 4][i % 4] = int(v, 16)
-    return [v for r in ymm for v in r], b"".join(v.to_bytes(8, "little") for v in win)
-
-
-def case_regs(c, regs, yin):
-    for i in range(16):
-        regs.gpr[i] = int(c["in"][i], 16)
-    regs.rflags = int(c["fl"], 16) | 0x200
-    set_ymm(regs, yin)
-    regs.mxcsr = int(c["mx"], 16)
-    return regs
-
-
-def window_after(c, win):
-    w = bytearray(win)
-    for i, v in c.get("mdiff", []):
-        w[i] = v
-    return bytes(w)
+DOC = AVX2X.doc
 
 
 def oracle_step(code, buf_va, win, setup):
     sp, regs = layout(code, buf_va, win)
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    o = oracle_of(sp)
     o.restore(setup(regs))
     ex = o.step()
     return o, ex, o.regs()
@@ -69,35 +30,13 @@ def oracle_step(code, buf_va, win, setup):
 
 @pytest.mark.parametrize("chunk", range(2))
 def test_oracle_matches_native_avx2x(chunk):
-    buf_va = int(DOC["buf_va"], 16)
     cases = DOC["cases"][chunk::2]
-    fails = []
-    for c in cases:
-        yin, win = inputs(c)
-        o, ex, r = oracle_step(bytes.fromhex(c["code"]), buf_va, win, lambda regs: case_regs(c, regs, yin))
-        ymm = get_ymm([r.xmm[i][h] for i in range(16) for h in range(2)], [r.ymmh[i][h] for i in range(16) for h in range(2)])
-        bad = check(c, ex.status, ex.vector, r.gpr, r.rflags, ymm, r.mxcsr, yin)
-        if not bad and o.read_virt(buf_va, 256) != window_after(c, win):
-            bad = ("mem",)
-        if bad:
-            fails.append((c["name"], c["code"], c["mx"]) + bad)
+    fails = run_family(AVX2X, replay_oracle, cases)
     assert not fails, f"{len(fails)}/{len(cases)} mismatches, first: {fails[:5]}"
 
 
 def test_engine_avx2x_code_matches_native_vectors():
-    L = sim_lib()
-    buf_va = int(DOC["buf_va"], 16)
-    fails = []
-    for c in DOC["cases"]:
-        yin, win = inputs(c)
-        sp, regs = layout(bytes.fromhex(c["code"]), buf_va, win)
-        out = sim_run(L, sp, case_regs(c, regs, yin), win_va=buf_va)
-        bad = check(c, out.status, out.vector, out.gpr, out.rflags, get_ymm(list(out.xmm), list(out.ymmh)),
-                    out.mxcsr, yin)
-        if not bad and bytes(out.win[:256]) != window_after(c, win):
-            bad = ("mem",)
-        if bad:
-            fails.append((c["name"], c["code"], c["mx"]) + bad)
+    fails = run_family(AVX2X, replay_sim, DOC["cases"])
     assert not fails, f"{len(fails)}/{len(DOC['cases'])} mismatches, first: {fails[:5]}"
 
 
@@ -120,8 +59,8 @@ def _both(code, setup, buf_va=0x10000, win=bytes(256)):
     """(status, vector, regs) from the oracle and from the engine's host build."""
     o, ex, r = oracle_step(code, buf_va, win, setup)
     sp, regs = layout(code, buf_va, win)
-    out = sim_run(sim_lib(), sp, setup(regs), win_va=buf_va)
-    return (ex.status, ex.vector, r), (out.status, out.vector, out)
+    out, fin, _ = simlane.run(sp, setup(regs), win_va=buf_va)
+    return (ex.status, ex.vector, r), (out.status, out.vector, fin)
 
 
 GATHER_DD_L0 = bytes([0xC4, 0xE2, 0x71, 0x90, 0x04, 0x90])  # vpgatherdd xmm0, [rax + xmm2 * 4], xmm1
@@ -163,8 +102,7 @@ def test_gather_fault_keeps_the_done_elements():
         return regs
     (so, vo, ro), (se, ve, re) = _both(GATHER_DD_L0, setup, buf_va, win)
     assert so == se == EXIT_FAULT and vo == ve == 14
-    eng = get_ymm(list(re.xmm), list(re.ymmh))
-    orc = get_ymm([ro.xmm[i][h] for i in range(16) for h in range(2)], [ro.ymmh[i][h] for i in range(16) for h in range(2)])
+    eng, orc = get_ymm(re), get_ymm(ro)
     assert eng[:12] == orc[:12]
     assert eng[0] == int.from_bytes(win[0:8], "little")               # elements 0 (index 0), 1 (index 1)
     assert eng[1] == 0x3333333344444444                               # elements 2, 3: untouched

@@ -10,85 +10,19 @@ judged by the same check() on every case; the recorded routines
 here, the random programs' EVEX pool (tests/progfuzz.py) may compare the engine
 with it. The GPU runs the same vectors in tests/test_gpu_avx512x.py.
 """
-import ctypes as C
-import gzip
-import json
-import os
-
 import pytest
 
-from tests.golden.gen_avx512_vectors import BOUND, case_inputs, guard_window
-from tests.golden.gen_avx512x_programs import GPR_INDEX, source
+from tests import simlane
+from tests.avx512x_programs import PROGS, program_case, program_check, program_space
 from tests.golden.gen_avx512x_vectors import forms, lengths
-from tests.oracle_lib import Oracle
-from tests.test_avx512 import WIN, XCR0, address_space, case_regs, check, get_zmm, sim_full
-from tests.test_sse import CODE_VA, SimResult
-from wtf_amd.abi import EXIT_FAULT, EXIT_INT3, EXIT_UNIMPLEMENTED, Regs, regs_from_state
+from tests.insn_cases import CODE_VA, get_zmm, oracle_of
+from tests.vector_replay import AVX512X, replay_oracle, replay_sim, run_family
+from wtf_amd.abi import EXIT_FAULT, EXIT_INT3, EXIT_UNIMPLEMENTED, regs_from_state
 from wtf_amd.tools.snapshot import AddressSpace, user_state
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def load():
-    with gzip.open(os.path.join(HERE, "golden", "avx512x_vectors.json.gz"), "rt") as f:
-        return json.load(f)
-
-
-DOC = load()
+DOC = AVX512X.doc
+inputs = AVX512X.inputs
 FAMILY = {f["nm"]: f["fam"] for f in forms()}
-with gzip.open(os.path.join(HERE, "golden", "avx512x_programs.json.gz"), "rt") as _f:
-    PROGS = json.load(_f)   # tests/golden/gen_avx512x_programs.py
-
-
-def inputs(c):
-    """(zmm0-31 as 256 u64, the window): case_inputs(seed), then the case's
-    deliberate inputs (zov: whole registers, wov: window bytes), then the guard."""
-    zmm, win = case_inputs(int(c["seed"], 16))
-    zmm = [list(v) for v in zmm]
-    for r, q in c.get("zov", []):
-        zmm[r] = [int(v, 16) for v in q]
-    win = bytearray(win)
-    for off, hx in c.get("wov", []):
-        bs = bytes.fromhex(hx)
-        win[off: off + len(bs)] = bs
-    return [v for r in zmm for v in r], guard_window(bytes(win), c["guard"])
-
-
-def sim_case(L, c, fast=False):
-    buf_va = int(DOC["buf_va"], 16)
-    zin, win = inputs(c)
-    sp = address_space(bytes.fromhex(c["code"]) + b"\xcc", buf_va, win, c["guard"])
-    regs = case_regs(c, regs_from_state(user_state(CODE_VA, 0, sp.cr3)), zin)
-    pfns, blob = sp.phys()
-    arr = (C.c_uint64 * len(pfns))(*pfns)
-    out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
-    L.sim_run_full(arr, blob, len(pfns), C.byref(regs), 0, C.byref(out), 1 if fast else 0, C.byref(cnt), buf_va,
-                   C.byref(fin), None)
-    if out.icount != (0 if "fault" in c else 1):
-        return ("icount", out.icount, out.status, out.vector)
-    return check(c, out.status, out.vector, out.error, out.addr, list(out.gpr), out.rflags, get_zmm(fin),
-                 list(fin.k), bytes(out.win[:WIN]), zin, win)
-
-
-def oracle_case(c):
-    """One case through the oracle (oracle/x86_oracle_avx512x.inc), as
-    tests/test_avx512.py's oracle_case does for U47, with this file's inputs."""
-    buf_va = int(DOC["buf_va"], 16)
-    zin, win = inputs(c)
-    sp = address_space(bytes.fromhex(c["code"]) + b"\xcc", buf_va, win, c["guard"])
-    regs = regs_from_state(user_state(CODE_VA, 0, sp.cr3))
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
-    o.restore(case_regs(c, regs, zin))
-    ex = o.step()
-    if o.icount() != (0 if "fault" in c else 1):
-        return ("icount", o.icount(), ex.status, ex.vector)
-    r = o.regs()
-    g = c["guard"]
-    mem = (bytes(BOUND) if g == 2 else o.read_virt(buf_va, BOUND)) + \
-        (bytes(WIN - BOUND) if g == 1 else o.read_virt(buf_va + BOUND, WIN - BOUND))
-    return check(c, ex.status, ex.vector, ex.error, ex.addr, list(r.gpr), r.rflags, get_zmm(r), list(r.k), mem,
-                 zin, win)
 
 
 @pytest.mark.parametrize("chunk", range(2))
@@ -99,11 +33,7 @@ def test_oracle_matches_native_avx512x(chunk):
     and address."""
     assert len(DOC["cases"]) == 4453
     cases = DOC["cases"][chunk::2]
-    fails = []
-    for c in cases:
-        bad = oracle_case(c)
-        if bad:
-            fails.append((c["name"], c["code"]) + bad)
+    fails = run_family(AVX512X, replay_oracle, cases)
     assert not fails, f"{len(fails)}/{len(cases)} mismatches, first: {fails[:5]}"
 
 
@@ -111,12 +41,7 @@ def test_oracle_matches_native_avx512x(chunk):
 def test_engine_avx512x_code_matches_native_vectors(fast):
     """The engine's decode / exec built for the host (tests/native/sim_lane.cc);
     fast=True goes through k_run's fast-loop digest first (EVEX stays generic)."""
-    L = sim_full()
-    fails = []
-    for c in DOC["cases"]:
-        bad = sim_case(L, c, fast)
-        if bad:
-            fails.append((c["name"], c["code"]) + bad)
+    fails = run_family(AVX512X, replay_sim, DOC["cases"], fast=fast)
     assert not fails, f"{len(fails)}/{len(DOC['cases'])} mismatches, first: {fails[:5]}"
 
 
@@ -240,24 +165,21 @@ STILL_OUTSIDE = {
 
 @pytest.mark.parametrize("name", sorted(STILL_OUTSIDE))
 def test_evex_forms_outside_the_subset_stay_unimplemented(name):
-    L = sim_full()
     c = next(c for c in DOC["cases"] if c["guard"] == 0 and "fault" not in c)
-    buf_va = int(DOC["buf_va"], 16)
-    zin, win = inputs(c)
-    sp = address_space(bytes.fromhex(STILL_OUTSIDE[name]) + b"\xcc", buf_va, win, 0)
-    regs = case_regs(c, regs_from_state(user_state(CODE_VA, 0, sp.cr3)), zin)
+    buf_va = AVX512X.buf_va
+    regs = regs_from_state(user_state(CODE_VA, 0, AddressSpace().cr3))
+    AVX512X.init(regs)
+    win = AVX512X.setup(c, regs)
+    zin = get_zmm(regs)
+    sp = AVX512X.space(bytes.fromhex(STILL_OUTSIDE[name]) + b"\xcc", CODE_VA, win, 0)
     regs.gpr[0] = buf_va
     regs.k[1] = 1
-    pfns, blob = sp.phys()
-    arr = (C.c_uint64 * len(pfns))(*pfns)
-    for fast in (0, 1):
-        out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
-        L.sim_run_full(arr, blob, len(pfns), C.byref(regs), 0, C.byref(out), fast, C.byref(cnt), buf_va,
-                       C.byref(fin), None)
+    for fast in (False, True):
+        out, _, _ = simlane.run(sp, regs, fast=fast, win_va=buf_va)
         assert out.status == EXIT_UNIMPLEMENTED and out.status not in (EXIT_FAULT, EXIT_INT3), (name, out.status,
                                                                                                   out.vector)
     # the oracle ends them the same way, with nothing retired and nothing changed
-    o = Oracle(pfns=pfns, blob=blob)
+    o = oracle_of(sp)
     o.restore(regs)
     ex = o.step()
     assert (ex.status, o.icount()) == (EXIT_UNIMPLEMENTED, 0), (name, ex.status, ex.vector)
@@ -266,53 +188,10 @@ def test_evex_forms_outside_the_subset_stay_unimplemented(name):
 
 
 # ---------------------------------------------------------------- the multi-instruction routines
-def program_space():
-    """The routines at CODE_VA; four pages at the native run's buffer address:
-    source (per case), constants, and the two destination areas."""
-    lay = PROGS["layout"]
-    buf_va = int(PROGS["buf_va"], 16)
-    sp = AddressSpace()
-    sp.map_range(CODE_VA, bytes.fromhex(PROGS["code"]), write=False)
-    for off in (lay["src"], lay["dst"], lay["dst2"]):
-        sp.map(buf_va + off, b"")
-    sp.map(buf_va + lay["consts"], bytes.fromhex(PROGS["consts"]))
-    return sp
-
-
-def program_case(c, regs):
-    """Set a lane's registers for case c (the arguments the native harness
-    passed; every other GPR a value no routine relies on); returns its source bytes."""
-    lay = PROGS["layout"]
-    buf_va = int(PROGS["buf_va"], 16)
-    for i in range(16):
-        if i != 4:
-            regs.gpr[i] = 0x1111111111111111 * i
-    regs.gpr[7], regs.gpr[6] = buf_va + lay["src"], buf_va + lay["dst"]
-    regs.gpr[2], regs.gpr[1] = c["len"], buf_va + lay["consts"]
-    regs.rip = CODE_VA + PROGS["routines"][c["routine"]]["entry"]
-    regs.xcr0 = XCR0
-    return source(c["routine"], c["seed"])
-
-
-def program_check(c, icount, gpr, dst, dst2):
-    if icount != c["icount"]:
-        return ("icount", icount, c["icount"])
-    want = {nm: int(v, 16) for nm, v in zip(PROGS["gprs"], c["gpr"])}
-    got = {nm: gpr[GPR_INDEX[nm]] for nm in want}
-    if got != want:
-        return ("gpr", {nm: (hex(got[nm]), hex(want[nm])) for nm in want if got[nm] != want[nm]})
-    if dst != bytes.fromhex(c["dst"]):
-        return ("dst", [i for i in range(len(dst)) if dst[i] != bytes.fromhex(c["dst"])[i]][:8])
-    if dst2 != bytes.fromhex(c["dst2"]):
-        return ("dst2", [i for i in range(len(dst2)) if dst2[i] != bytes.fromhex(c["dst2"])[i]][:8])
-    return None
-
-
 @pytest.mark.parametrize("fast", [False, True], ids=["exec", "fast"])
 def test_engine_runs_avx512x_programs(fast):
     """The natively recorded routines through the engine's host build, to their
     int3: the retired count, the GPRs and both destination areas of every case."""
-    L = sim_full()
     lay = PROGS["layout"]
     buf_va = int(PROGS["buf_va"], 16)
     assert {c["routine"] for c in PROGS["cases"]} == set(PROGS["routines"]) and len(PROGS["cases"]) == 32
@@ -321,21 +200,17 @@ def test_engine_runs_avx512x_programs(fast):
         sp = program_space()
         regs = regs_from_state(user_state(CODE_VA, 0, sp.cr3))
         sp.write(buf_va + lay["src"], program_case(c, regs))
-        pfns, blob = sp.phys()
-        arr = (C.c_uint64 * len(pfns))(*pfns)
-        out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
-        ov = (C.c_uint8 * (64 * 4096))()
-        L.sim_run_full(arr, blob, len(pfns), C.byref(regs), 0, C.byref(out), 1 if fast else 0, C.byref(cnt), 0,
-                       C.byref(fin), ov)
+        ov = simlane.page_buffer()
+        out, _, cnt = simlane.run(sp, regs, fast=fast, pages=ov)
         if out.status != EXIT_INT3:
             fails.append((c["routine"], c["len"], "exit", out.status, out.vector, hex(out.rip)))
             continue
-        dirty = {out.dirty[k]: bytes(ov[4096 * k: 4096 * k + 4096]) for k in range(min(out.ovn, 64))}
+        dirty = simlane.dirty_pages(out, ov)
         area = [dirty.get(sp.translate(buf_va + lay[k]), bytes(4096))[:lay["area"]] for k in ("dst", "dst2")]
         bad = program_check(c, out.icount, list(out.gpr), area[0], area[1])
         if bad:
             fails.append((c["routine"], c["len"]) + bad)
-        assert not fast or cnt.value > 0   # the VEX moves and the integer code took the fast loop's forms
+        assert not fast or cnt > 0   # the VEX moves and the integer code took the fast loop's forms
     assert not fails, f"{len(fails)}/{len(PROGS['cases'])}, first: {fails[:4]}"
 
 
@@ -350,8 +225,7 @@ def test_oracle_runs_avx512x_programs():
         sp = program_space()
         regs = regs_from_state(user_state(CODE_VA, 0, sp.cr3))
         sp.write(buf_va + lay["src"], program_case(c, regs))
-        pfns, blob = sp.phys()
-        o = Oracle(pfns=pfns, blob=blob)
+        o = oracle_of(sp)
         o.restore(regs)
         o.set_limit(10 * c["icount"] + 1000)
         ex = o.run()
@@ -374,7 +248,6 @@ def test_engine_evex_code_matches_oracle_on_random_programs(fast, shared):
     zmm0-31, k0-7, MXCSR, the byte counter and the dirty set, per lane."""
     from tests import progfuzz
 
-    L = sim_full()
     n, seed = 192, 36
     if shared:
         sp, st, lanes = progfuzz.build_shared(n, 16, seed, sse=True, evex=True)
@@ -382,8 +255,7 @@ def test_engine_evex_code_matches_oracle_on_random_programs(fast, shared):
         sp, st, lanes = progfuzz.build(n, seed=seed, sse=True, evex=True)
     kw = progfuzz.lane_state(n, seed, True, True)
     want = progfuzz.oracle_run(sp, st, lanes, limit=2000, **kw)
-    pfns, blob = sp.phys()
-    arr = (C.c_uint64 * len(pfns))(*pfns)
+    img = simlane.image(sp)
     bad = []
     for i, ((va, g, flags), w) in enumerate(zip(lanes, want)):
         regs = regs_from_state(st)
@@ -391,9 +263,7 @@ def test_engine_evex_code_matches_oracle_on_random_programs(fast, shared):
             regs.gpr[k] = g[k]
         progfuzz.set_lane_state(regs, i, **kw)
         regs.rip, regs.rflags = va, flags
-        out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
-        L.sim_run_full(arr, blob, len(pfns), C.byref(regs), 2000, C.byref(out), 1 if fast else 0, C.byref(cnt), 0,
-                       C.byref(fin), None)
+        out, fin, _ = simlane.run(img, regs, limit=2000, fast=fast)
         f = out.status == EXIT_FAULT
         got = (out.status, out.vector if f else 0, out.error if f else 0, out.addr if f else 0, out.rip, out.icount)
         f = w["status"] == EXIT_FAULT

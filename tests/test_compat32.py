@@ -12,7 +12,6 @@ import pytest
 
 from tests import compat32 as T
 from tests import sysprog2 as S
-from tests.test_sys2 import _diff, sim_lanes, sim_lib
 from wtf_amd import abi
 from wtf_amd.abi import regs_from_state
 
@@ -149,11 +148,11 @@ def test_engine_code_matches_oracle(space):
     sp, st, lay, data = space
     ln = T.lanes(37 * 24, 21)
     want = S.oracle_run(sp, st, ln, limit=500)
-    got = sim_lanes(sim_lib(), sp, st, ln, limit=500)
+    got = S.sim_lanes(sp, st, ln, limit=500)
     names = {v: k for k, v in T.SLOT32.items()}
     bad = []
     for i, (w, g) in enumerate(zip(want, got)):
-        d = _diff(g, w)
+        d = S.diff(g, w)
         if d:
             bad.append((i, names[ln[i][1][3]], d, {k: (g[k], w[k]) for k in d if k not in ("pages", "xmm", "ymmh")}))
     assert not bad, f"{len(bad)}/{len(ln)} lanes differ; first: {bad[:3]}"
@@ -194,7 +193,7 @@ def test_gpu_matches_oracle(space):
             e = ex[i]
             pg = {gpa: eng.read_phys(i, gpa, 4096) for gpa in eng.dirty(i)}
             got = S.lane_view(e.status, e.vector, e.error, e.addr, e.icount, int(nb[i]), regs[i], pg)
-            d = _diff(got, w)
+            d = S.diff(got, w)
             if d:
                 bad.append((i, d, {k: (got[k], w[k]) for k in d if k not in ("pages", "xmm", "ymmh")}))
         assert not bad, f"{len(bad)}/{n} lanes differ; first: {bad[:3]}"
@@ -240,8 +239,8 @@ def test_random_instruction_bytes_in_32_bit_mode_engine_equals_oracle():
     agree lane by lane on every exit, register and page."""
     sp, st, lanes = _random_32bit_programs()
     want = S.oracle_run(sp, st, lanes, limit=2000)
-    got = sim_lanes(sim_lib(), sp, st, lanes, limit=2000)
-    bad = [(i, _diff(g, w)) for i, (g, w) in enumerate(zip(got, want)) if _diff(g, w)]
+    got = S.sim_lanes(sp, st, lanes, limit=2000)
+    bad = [(i, S.diff(g, w)) for i, (g, w) in enumerate(zip(got, want)) if S.diff(g, w)]
     assert not bad, f"{len(bad)}/{len(lanes)} lanes differ; first: {bad[:3]}"
     kinds = {(w["exit"][0], w["exit"][1]) for w in want}
     assert len(kinds) >= 4, kinds
@@ -278,7 +277,7 @@ def test_gpu_random_instruction_bytes_in_32_bit_mode():
             e = ex[i]
             pg = {gpa: eng.read_phys(i, gpa, 4096) for gpa in eng.dirty(i)}
             got = S.lane_view(e.status, e.vector, e.error, e.addr, e.icount, int(nb[i]), out[i], pg)
-            d = _diff(got, w)
+            d = S.diff(got, w)
             if d:
                 bad.append((i, d))
         assert not bad, f"{len(bad)}/{n} lanes differ; first: {bad[:3]}"

@@ -86,7 +86,6 @@ def test_twin_edges_add_coverage(tmp_path):
 
 @pytest.mark.gpu
 def test_gpu_edges_match_oracle_on_random_programs():
-    from tests.test_gpu_progfuzz import run_gpu
 
     n = 512
     sp, st, lanes = progfuzz.build(n, seed=41)

@@ -9,39 +9,26 @@ memory window, and the vector moves the guests' memcpy / memset loops run
 ends and with the SSE / AVX state switched off, against the generic path and
 the oracle.
 """
-import ctypes as C
-import gzip
-import json
-import os
-
 import pytest
 
-from tests.golden.gen_native_vectors import splitmix_bytes
-from tests.golden.gen_sse_vectors import window_in
-from tests.oracle_lib import Oracle
-from tests.test_sse import BUF, SimResult, layout, sim_lib, sim_run
-from wtf_amd.abi import EXIT_FAULT, Regs
+from tests import simlane
+from tests.insn_cases import BUF, CODE_VA, get_zmm, layout, move_case, oracle_of, widening_program
+from tests.vector_replay import AVX, NATIVE, SSE, cpu_case, replay_sim
+from wtf_amd.abi import EXIT_FAULT
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 INT3 = 3
 
 
-def vectors(name):
-    with gzip.open(os.path.join(HERE, "golden", name), "rt") as f:
-        return json.load(f)
-
-
-def run_both(L, sp, regs, win_va, limit=0):
-    """(slow result, fast result, instructions the fast forms retired)."""
-    cnt = C.c_uint64(0)
-    slow = sim_run(L, sp, regs, limit=limit, win_va=win_va)
-    fast = sim_run(L, sp, regs, limit=limit, fast=True, counter=cnt, win_va=win_va)
-    return slow, fast, cnt.value
+def run_both(sp, regs, win_va, limit=0):
+    """(slow result, fast result, instructions the fast forms retired, slow's final registers, fast's)."""
+    slow, fs, _ = simlane.run(sp, regs, limit=limit, win_va=win_va)
+    fast, ff, n = simlane.run(sp, regs, limit=limit, fast=True, win_va=win_va)
+    return slow, fast, n, fs, ff
 
 
 def same(a, b, fa=None, fb=None):
-    """fa / fb: the two runs' final register files where the run returned them
-    (sim_run_full): zmm0-15's bits 511:256, zmm16-31 and k0-7 are compared too."""
+    """fa / fb: the two runs' final register files: zmm0-15's bits 511:256,
+    zmm16-31 and k0-7 are compared too."""
     full = fa is None or (bytes(fa.zmmh) == bytes(fb.zmmh) and bytes(fa.zmm_hi) == bytes(fb.zmm_hi) and
                           list(fa.k) == list(fb.k) and fa.xcr0 == fb.xcr0)
     return (a.status == b.status and a.vector == b.vector and a.rip == b.rip and a.icount == b.icount and
@@ -49,74 +36,25 @@ def same(a, b, fa=None, fb=None):
             list(a.ymmh) == list(b.ymmh) and a.nbytes == b.nbytes and bytes(a.win) == bytes(b.win) and full)
 
 
-def run_both_full(L, sp, regs, win_va, limit=0):
-    """run_both through sim_run_full: (slow, fast, fast-form count, slow's final registers, fast's)."""
-    pfns, blob = sp.phys()
-    arr = (C.c_uint64 * len(pfns))(*pfns)
-    res = []
-    cnt = C.c_uint64(0)
-    for fast in (0, 1):
-        out, fin = SimResult(), Regs()
-        L.sim_run_full(arr, blob, len(pfns), C.byref(regs), limit, C.byref(out), fast, C.byref(cnt), win_va,
-                       C.byref(fin), None)
-        res.append((out, fin))
-    return res[0][0], res[1][0], cnt.value, res[0][1], res[1][1]
-
-
 def test_integer_vectors_through_fast_forms():
-    doc = vectors("native_vectors.json.gz")
-    L = sim_lib()
-    buf_va = int(doc["buf_va"], 16)
+    cases = NATIVE.doc["cases"]
     fails, fast_total = [], 0
-    for c in doc["cases"]:
-        sp, regs = layout(bytes.fromhex(c["code"]), buf_va, splitmix_bytes(int(c["seed"], 16), 256))
-        for i in range(16):
-            regs.gpr[i] = int(c["in"][i], 16)
-        regs.rflags = int(c["fl"], 16) | 0x200
-        cnt = C.c_uint64(0)
-        out = sim_run(L, sp, regs, fast=True, counter=cnt, win_va=buf_va)
-        fast_total += cnt.value
-        want = [int(x, 16) for x in c["out"]]
-        got = list(out.gpr)
-        if c["cls"] == "bsx" and (int(c["flo"], 16) & 0x40):
-            got[c["dst"]] = want[c["dst"]]
-        win = bytearray(splitmix_bytes(int(c["seed"], 16), 256))
-        for i, v in c["diff"]:
-            win[i] = v
-        if out.status != INT3 or out.icount != 1:
-            fails.append((c["name"], "exit", out.status))
-        elif got != want or (out.rflags ^ int(c["flo"], 16)) & int(c["fmask"], 16):
-            fails.append((c["name"], "regs"))
-        elif bytes(out.win[:256]) != bytes(win):
-            fails.append((c["name"], "mem"))
+    for c, o in zip(cases, replay_sim(NATIVE, cases, fast=True), strict=True):
+        fast_total += o.fast
+        bad = NATIVE.check(c, o)
+        if bad:
+            fails.append((c["name"],) + bad)
     assert not fails, f"{len(fails)} mismatches, first: {fails[:6]}"
-    assert fast_total > len(doc["cases"]) // 3, fast_total
+    assert fast_total > len(cases) // 3, fast_total
 
 
 @pytest.mark.parametrize("name", ["sse_vectors.json.gz", "avx_vectors.json.gz"])
 def test_vector_vectors_fast_equals_slow(name):
-    doc = vectors(name)
-    L = sim_lib()
-    buf_va = int(doc["buf_va"], 16)
-    avx = name.startswith("avx")
+    fam = AVX if name.startswith("avx") else SSE
     fails, fast_total = [], 0
-    for c in doc["cases"]:
-        win = splitmix_bytes(int(c["seed"], 16), 256) if avx else window_in(int(c["seed"], 16), c["ldmx"])
-        sp, regs = layout(bytes.fromhex(c["code"]), buf_va, win)
-        for i in range(16):
-            regs.gpr[i] = int(c["in"][i], 16)
-        regs.rflags = int(c["fl"], 16) | 0x200
-        if avx:
-            ys = [int(v, 16) for v in c["yin"]]
-            for i in range(16):
-                regs.xmm[i][0], regs.xmm[i][1] = ys[4 * i], ys[4 * i + 1]
-                regs.ymmh[i][0], regs.ymmh[i][1] = ys[4 * i + 2], ys[4 * i + 3]
-        else:
-            xs = [int(v, 16) for v in c["xin"]]
-            for i in range(16):
-                regs.xmm[i][0], regs.xmm[i][1] = xs[2 * i], xs[2 * i + 1]
-            regs.mxcsr = int(c["mx"], 16)
-        slow, fast, n = run_both(L, sp, regs, buf_va)
+    for c in fam.doc["cases"]:
+        sp, regs, win = cpu_case(fam, c)
+        slow, fast, n = run_both(sp, regs, fam.buf_va)[:3]
         fast_total += n
         want = bytearray(win)
         for i, v in c["diff"]:
@@ -162,30 +100,15 @@ MOVES = {
 PRIV = "8a078807"  # mov al, [rdi]; mov [rdi], al: the destination page becomes the lane's own first
 
 
-def move_case(code_hex, off_src, off_dst, cr0=None, cr4=None, xcr0=None):
-    code = bytes.fromhex(code_hex)
-    page = BUF & ~0xFFF
-    sp, regs = layout(code, page, bytes((i * 7 + 3) & 0xFF for i in range(4096)), cr0=cr0, cr4=cr4)
-    regs.gpr[6] = page + off_src  # rsi
-    regs.gpr[7] = page + off_dst  # rdi
-    for k in range(16):
-        regs.xmm[k][0], regs.xmm[k][1] = 0x1111111111111111 * (k + 1), 0x0101010101010101 * (k + 3)
-        regs.ymmh[k][0], regs.ymmh[k][1] = 0xA0A0A0A0A0A0A0A0 + k, 0xB0B0B0B0B0B0B0B0 + k
-    if xcr0 is not None:
-        regs.xcr0 = xcr0
-    return sp, regs
-
-
 @pytest.mark.parametrize("name", sorted(MOVES))
 def test_moves_fast_equals_slow_and_oracle(name):
-    L = sim_lib()
     page = BUF & ~0xFFF
     offsets = [(s, d) for s in (0, 1, 3, 7, 8, 13, 16, 24, 31) for d in (0, 2, 5, 8, 9, 16, 30)]
     offsets += [(4096 - 32, 4096 - 16), (4096 - 16, 4096 - 32), (4096 - 20, 4096 - 9), (4096 - 1, 4096 - 33)]
     fast_runs = 0
     for s, d in offsets:
         sp, regs = move_case(PRIV + MOVES[name], s, d)
-        slow, fast, n = run_both(L, sp, regs, page + 0x100 if max(s, d) < 0x100 else page + 4096 - 256)
+        slow, fast, n = run_both(sp, regs, page + 0x100 if max(s, d) < 0x100 else page + 4096 - 256)[:3]
         fast_runs += n
         assert same(slow, fast), (name, s, d, slow.status, fast.status)
         # the priming moves run fast too (the cold TLB and the copy-on-write are
@@ -195,8 +118,7 @@ def test_moves_fast_equals_slow_and_oracle(name):
         off = (d if "store" in name and "reg" not in name else s) if ("load" in name or "store" in name) else 0
         crosses = "reg" not in name and ("load" in name or "store" in name) and off + size > 4096
         assert n == 2 + (0 if slow.status != INT3 or crosses or name == "pxor other" else 1), (name, s, d, n)
-        pfns, blob = sp.phys()
-        o = Oracle(pfns=pfns, blob=blob)
+        o = oracle_of(sp)
         o.restore(regs)
         ex = o.run()
         r = o.regs()
@@ -216,7 +138,6 @@ def test_moves_fast_equals_slow_and_oracle(name):
 def test_vector_moves_defer_to_generic_when_state_is_off():
     """CR0.TS (#NM), CR0.EM / no OSFXSR (#UD), no OSXSAVE or XCR0 (#UD): the
     fast forms leave the lane to exec(), which raises the fault."""
-    L = sim_lib()
     cases = [
         ("f30f6f0e", dict(cr0=0x80050031 | 8), 7),
         ("f30f6f0e", dict(cr0=0x80050031 | 4), 6),
@@ -229,28 +150,9 @@ def test_vector_moves_defer_to_generic_when_state_is_off():
     ]
     for code, kw, vec in cases:
         sp, regs = move_case(code, 0, 64, **kw)
-        slow, fast, n = run_both(L, sp, regs, 0)
+        slow, fast, n = run_both(sp, regs, 0)[:3]
         assert (fast.status, fast.vector) == (EXIT_FAULT, vec), (code, kw, fast.status, fast.vector)
         assert same(slow, fast) and n == 0, (code, kw)
-
-
-def widening_program(vzu):
-    """A kernel stub that writes vector registers through VEX while XCR0 = 7,
-    then widens XCR0 to 0xe7 and stores zmm0 / 1 / 3 / 5 with vmovdqu64. A VEX
-    write zeroes the destination up to MAXVL (bits 511:128 / 511:256; SDM vol. 1
-    15.5) whatever XCR0 enables, so the stores show zeros there."""
-    from tests.golden.gen_avx512_vectors import evex
-
-    code = bytes.fromhex(
-        "0f05" "cccccccccccc"   # 0  syscall -> lstar = 8 (ring 0: xsetbv is privileged)
-        "c5fa6f0e"              # 8  vmovdqu xmm1, [rsi]    VEX.128 load
-        "c5fe6fda"              #    vmovdqu ymm3, ymm2     VEX.256 register move
-        + ("c5f877" if vzu else "") +  # vzeroupper
-        "b900000000" "b8e7000000" "ba00000000"  # mov ecx, 0; mov eax, 0xe7; mov edx, 0
-        "0f01d1")               #    xsetbv
-    for slot, reg in enumerate((0, 1, 3, 5)):
-        code += bytes(evex(1, 2, 1, 2, 0, 0, 0, reg, 0, 0x7F, mem=(7, None, 0, slot, 1)))  # vmovdqu64 [rdi + 64 * slot], zmm
-    return code
 
 
 @pytest.mark.parametrize("vzu", [False, True], ids=["moves", "moves-vzeroupper"])
@@ -258,10 +160,6 @@ def test_vex_writes_zero_to_maxvl_before_xcr0_is_widened(vzu):
     """Generic and fast give the same final registers and window, and both
     equal the oracle: the fast loop's VEX forms zero bits 511:256 as ymm_put
     does, not only while XCR0 enables the ZMM state."""
-    from tests.test_avx512 import get_zmm, sim_full
-    from tests.test_sse import CODE_VA
-
-    L = sim_full()
     page = BUF & ~0xFFF
     sp, regs = move_case(widening_program(vzu).hex(), 0x40, 0x100, xcr0=7)
     regs.cr4 &= ~(3 << 20)  # no SMEP / SMAP: the stub runs on the test's user code page
@@ -269,11 +167,10 @@ def test_vex_writes_zero_to_maxvl_before_xcr0_is_widened(vzu):
     for k in range(16):
         for h in range(4):
             regs.zmmh[k][h] = 0xC0C0C0C0C0C0C0C0 + 16 * k + h
-    slow, fast, n, fs, ff = run_both_full(L, sp, regs, page + 0x100)
+    slow, fast, n, fs, ff = run_both(sp, regs, page + 0x100)
     assert slow.status == INT3 and fast.status == INT3, (slow.status, slow.vector, fast.status, fast.vector)
     assert n >= 2 + (1 if vzu else 0), n   # the VEX moves (and vzeroupper) ran as fast forms
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    o = oracle_of(sp)
     o.restore(regs)
     ex = o.run()
     r = o.regs()
@@ -288,10 +185,9 @@ def test_vex_writes_zero_to_maxvl_before_xcr0_is_widened(vzu):
 
 
 def test_aligned_forms_fault_when_misaligned_on_fast_path():
-    L = sim_lib()
     for code in ("660f6f0e", "660f7f0f", "0f290f", "c5fd6f0e", "c5fd7f0f", "c5fc280e"):
         sp, regs = move_case(code, 8 if code.endswith("0e") else 0, 8)
-        slow, fast, _ = run_both(L, sp, regs, 0)
+        slow, fast, _ = run_both(sp, regs, 0)[:3]
         assert (fast.status, fast.vector) == (EXIT_FAULT, 13), code
         assert same(slow, fast), code
 
@@ -311,12 +207,11 @@ def test_copy_loop_program_fast_equals_slow():
         "f30f6f06"      # movdqu xmm0, [rsi]
         "f30f7f07"      # movdqu [rdi], xmm0
     )
-    L = sim_lib()
     page = BUF & ~0xFFF
     for s, d in ((0, 0), (1, 0), (3, 9), (16, 7), (5, 37)):
         sp, regs = move_case(prog.hex(), s, 0x400 + d)
         regs.gpr[1] = 20
-        slow, fast, n = run_both(L, sp, regs, page + 0x400)
+        slow, fast, n = run_both(sp, regs, page + 0x400)[:3]
         assert same(slow, fast), (s, d)
         assert fast.status == INT3 and n > 60, (s, d, fast.status, n)
         src = bytes((i * 7 + 3) & 0xFF for i in range(4096))
@@ -328,16 +223,14 @@ def test_copy_loop_program_fast_equals_slow():
 def test_opcodes_invalid_in_64bit_mode_raise_ud(op):
     """SDM opcode map (i64): #UD on the oracle and the engine's code, at the
     instruction, nothing retired (they were engine errors before)."""
-    L = sim_lib()
     code = bytes([op, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00])
     sp, regs = layout(code, BUF, bytes(256))
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    o = oracle_of(sp)
     o.restore(regs)
     ex = o.step()
     assert (ex.status, ex.vector) == (EXIT_FAULT, 6), hex(op)
     for fast in (False, True):
-        out = sim_run(L, sp, regs, fast=fast)
+        out = simlane.run(sp, regs, fast=fast)[0]
         assert (out.status, out.vector, out.icount, out.rip) == (EXIT_FAULT, 6, 0, regs.rip), (hex(op), fast)
 
 
@@ -346,7 +239,6 @@ def test_indirect_branches_unary_bit_and_segment_forms_fast_equals_slow():
     relative moves, not / neg, test with a memory operand, shifts by cl,
     bt / bts with register and immediate bit numbers, call [mem], call reg,
     jmp reg: the fast form gives the generic path's lane, and runs."""
-    from tests.test_sse import CODE_VA
     code = bytes.fromhex(
         "65488b042510000000"   # 0  mov rax, gs:[0x10]
         "6548890425 18000000"  # 9  mov gs:[0x18], rax
@@ -375,11 +267,10 @@ def test_indirect_branches_unary_bit_and_segment_forms_fast_equals_slow():
     win[8:16] = (0xF0F0).to_bytes(8, "little")
     win[16:24] = (CODE_VA + 60).to_bytes(8, "little")
     win[0x110:0x118] = (0xDEADBEEF).to_bytes(8, "little")
-    L = sim_lib()
     sp, regs = layout(code, page, bytes(win))
     regs.gpr[4], regs.gpr[7], regs.gpr[1], regs.gpr[2] = page + 0x800, page, 5, 0xFF
     regs.seg[5].base = page + 0x100  # gs
-    slow, fast, n = run_both(L, sp, regs, page)
+    slow, fast, n = run_both(sp, regs, page)[:3]
     assert same(slow, fast)
     assert fast.status == INT3 and fast.rip == CODE_VA + 83, (fast.status, hex(fast.rip))
     assert n == 16, n  # every instruction but the trailing int3 ran on the fast path
@@ -391,7 +282,6 @@ def test_high_byte_register_forms_fast_equals_slow_and_oracle():
     path: read as bits 15:8 of rax..rbx, written merged into those bits, for
     mov / ALU / test / inc / not / neg / shifts / setcc / movzx / movsx and the
     memory forms; the fast forms give the generic path's and the oracle's lane."""
-    from tests.test_sse import CODE_VA
     code = bytes.fromhex(
         "f6c510"        # test ch, 0x10
         "88e0"          # mov al, ah
@@ -416,16 +306,14 @@ def test_high_byte_register_forms_fast_equals_slow_and_oracle():
         .replace(" ", ""))
     page = BUF & ~0xFFF
     win = bytearray(range(256)) * 2
-    L = sim_lib()
     sp, regs = layout(code, page, bytes(win))
     regs.gpr[0], regs.gpr[1], regs.gpr[2], regs.gpr[3] = (0x1122334455667788, 0x99AABBCCDDEEFF10,
                                                           0x0F1E2D3C4B5A6978, 0x8070605040302010)
     regs.gpr[7] = page
-    slow, fast, n = run_both(L, sp, regs, page)
+    slow, fast, n = run_both(sp, regs, page)[:3]
     assert same(slow, fast)
     assert n == 20, n  # every form ran fast
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    o = oracle_of(sp)
     o.restore(regs)
     ex = o.run()
     r = o.regs()
@@ -441,7 +329,6 @@ def test_system_call_forms_fast_equals_slow_and_oracle():
     generic step (a fast form for them cost more in register pressure than it
     saved); only the mov runs fast. At ring 3,
     swapgs and sysretq raise #GP as exec() does."""
-    from tests.test_sse import CODE_VA
     code = bytes.fromhex(
         "0f05"                  # 0  syscall -> lstar = 8
         "cc" "cccccccccc"       # 2  int3 (sysretq returns here)
@@ -450,20 +337,18 @@ def test_system_call_forms_fast_equals_slow_and_oracle():
         "0f01f8"                # 18 swapgs
         "480f07")               # 21 sysretq
     page = BUF & ~0xFFF
-    L = sim_lib()
     sp, regs = layout(code, page, bytes(256))
     regs.cr4 &= ~(3 << 20)  # no SMEP / SMAP: the stub runs on the test's user code page
     regs.lstar = CODE_VA + 8
     regs.kernel_gs_base = 0xAAAA000
     regs.seg[5].base = 0xBBBB000
     regs.gpr[11] = 0x55
-    slow, fast, n = run_both(L, sp, regs, page)
+    slow, fast, n = run_both(sp, regs, page)[:3]
     assert same(slow, fast)
     assert fast.status == INT3 and fast.rip == CODE_VA + 2, (fast.status, hex(fast.rip))
     assert fast.gpr[0] == 0x1234 and fast.gpr[1] == CODE_VA + 2
     assert n == 1, n  # the mov; the system forms run on the generic step
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    o = oracle_of(sp)
     o.restore(regs)
     ex = o.run()
     r = o.regs()
@@ -472,5 +357,5 @@ def test_system_call_forms_fast_equals_slow_and_oracle():
     # ring 3: swapgs / sysretq are #GP(0), raised by the slow step
     for op in ("0f01f8", "480f07"):
         sp, regs = layout(bytes.fromhex(op), page, bytes(256))
-        slow, fast, n = run_both(L, sp, regs, page)
+        slow, fast, n = run_both(sp, regs, page)[:3]
         assert same(slow, fast) and (fast.status, fast.vector) == (EXIT_FAULT, 13) and n == 0, (op, fast.status)

@@ -4,8 +4,10 @@ tests/golden/gen_avx512x_programs.py through k_run (uop cache, fast loop <->
 generic step, the cold zmm state shared by both)."""
 import pytest
 
-from tests.test_avx512x import DOC, PROGS, inputs, program_case, program_check, program_space
-from wtf_amd.abi import EXIT_FAULT, EXIT_INT3, EXIT_UNIMPLEMENTED, regs_from_state
+from tests import vector_replay as V
+from tests.avx512x_programs import PROGS, program_case, program_check, program_space
+from tests.insn_cases import CODE_VA
+from wtf_amd.abi import EXIT_INT3, EXIT_UNIMPLEMENTED, regs_from_state
 from wtf_amd.tools.snapshot import user_state
 
 pytestmark = pytest.mark.gpu
@@ -16,67 +18,10 @@ def test_gpu_matches_native_avx512x_vectors():
     window across a page boundary; the guard cases (one of the two pages
     absent) in their own address spaces, one engine per guard value, as
     test_gpu_matches_native_avx512_vectors does."""
-    from tests.test_avx512 import BOUND, WIN, XCR0, address_space, case_regs, check, get_zmm
-    from tests.test_avx512 import CODE_VA as CVA
-    from wtf_amd.engine import Engine
-
-    buf_va = int(DOC["buf_va"], 16)
-    fails = []
-    total = 0
-    for guard in (0, 1, 2):
-        cases = [c for c in DOC["cases"] if c["guard"] == guard]
-        total += len(cases)
-        codes = sorted({c["code"] for c in cases})
-        slot = {c: i for i, c in enumerate(codes)}
-        blob = bytearray(32 * len(codes))
-        for c, i in slot.items():
-            b = bytes.fromhex(c) + b"\xcc"
-            blob[32 * i: 32 * i + len(b)] = b
-        sp = address_space(bytes(blob), buf_va, bytes(WIN), guard)
-        n = (len(cases) + 63) // 64 * 64
-        eng = Engine(0)
-        pfns, pblob = sp.phys()
-        eng.load_pool(pfns, pblob)
-        eng.alloc_lanes(n, overlay_pages=4, cov_entries=64)
-        init = regs_from_state(user_state(CVA, 0, sp.cr3))
-        init.xcr0 = XCR0
-        eng.set_initial_state(init)
-        eng.set_limit(0)
-        eng.restore()
-        regs = eng.read_regs(0, n)
-        writes, ins, wins = [], [], []
-        for i, c in enumerate(cases):
-            zin, win = inputs(c)
-            ins.append(zin)
-            wins.append(win)
-            r = case_regs(c, regs[i], zin)
-            r.rip = CVA + 32 * slot[c["code"]]
-            if guard != 2:
-                writes.append((i, buf_va, win[:BOUND]))
-            if guard != 1:
-                writes.append((i, buf_va + BOUND, win[BOUND:]))
-        for i in range(len(cases), n):
-            regs[i].rip = CVA + 32 * slot[cases[0]["code"]] + len(bytes.fromhex(cases[0]["code"]))
-        eng.write_regs(regs)
-        eng.apply_writes(writes)
-        eng.run()
-        ex = eng.exits()
-        out = eng.read_regs(0, n)
-        for i, c in enumerate(cases):
-            r, e = out[i], ex[i]
-            if "fault" not in c and (e.status != EXIT_INT3 or e.icount != 1):
-                fails.append((c["name"], c["code"], "exit", e.status, e.vector))
-                continue
-            if "fault" in c and e.status != EXIT_FAULT:
-                fails.append((c["name"], c["code"], "no fault", e.status))
-                continue
-            lo = bytes(BOUND) if guard == 2 else eng.read_virt(i, buf_va, BOUND)
-            hi = bytes(WIN - BOUND) if guard == 1 else eng.read_virt(i, buf_va + BOUND, WIN - BOUND)
-            bad = check(c, e.status, e.vector, e.error, e.addr, list(r.gpr), r.rflags, get_zmm(r), list(r.k),
-                        lo + hi, ins[i], wins[i])
-            if bad:
-                fails.append((c["name"], c["code"]) + bad)
-    assert total == len(DOC["cases"])
+    cases = V.AVX512X.doc["cases"]
+    fails = V.run_family(V.AVX512X, V.replay_gpu, cases)
+    total = len(cases)
+    assert total == len(V.AVX512X.doc["cases"])
     assert not fails, f"{len(fails)}/{total} mismatches, first: {fails[:6]}"
 
 
@@ -86,8 +31,6 @@ def test_gpu_runs_avx512x_programs():
     every wave so its lanes leave their loops at different steps. Per lane: the
     int3 exit, the retired count the native run implies, both destination areas
     and the GPRs; no lane UNIMPLEMENTED."""
-    from tests.test_avx512 import XCR0
-    from tests.test_sse import CODE_VA
     from wtf_amd.engine import Engine
 
     n = 320
@@ -99,7 +42,7 @@ def test_gpu_runs_avx512x_programs():
     eng.load_pool(pfns, pblob)
     eng.alloc_lanes(n, overlay_pages=8, cov_entries=64)
     init = regs_from_state(user_state(CODE_VA, 0, sp.cr3))
-    init.xcr0 = XCR0
+    init.xcr0 = V.XCR0
     eng.set_initial_state(init)
     eng.set_limit(0)
     eng.restore()

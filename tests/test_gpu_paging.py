@@ -15,11 +15,10 @@ import pytest
 
 from wtf_amd import abi
 
+from tests import launch_shapes as shared
 from tests import paging_cases as Z
 from tests import paging_model as M
-from tests import test_gpu_progfuzz_shared as shared
 from tests.oracle_lib import Oracle
-from tests.test_paging import ASSERTED, HOST_WRITES, _host_addresses, diff
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +31,10 @@ CODE_ON_LEAF = {"t-x-2m-cross4k": [Z.L2 + 0xFFD], "t-x-2m-out-present": [Z.L2 + 
 def _mixed():
     """Every case on a lane of its own, shuffled with a fixed seed, padded with
     repeats to whole waves: [(case, salt)]."""
-    lanes = [(c, 0) for c in ASSERTED]
+    lanes = [(c, 0) for c in Z.ASSERTED]
     rnd = random.Random(20260401)
     while len(lanes) % 64:
-        lanes.append((rnd.choice(ASSERTED), 1 + len(lanes) % 200))
+        lanes.append((rnd.choice(Z.ASSERTED), 1 + len(lanes) % 200))
     rnd.shuffle(lanes)
     assert len(lanes) >= 256
     rings = [{c.cpl for c, _ in lanes[i:i + 64]} for i in range(0, len(lanes), 64)]
@@ -46,7 +45,7 @@ def _mixed():
 # the cases that copy a page, by the model's word: every case that ends with a dirty frame (stores through
 # aliases, CR0.WP = 0 stores, stores into and out of large leaves and into the frame the dump does not
 # hold, table edits)
-UNIFORM = [c for c in ASSERTED if Z.expect(c).dirty]
+UNIFORM = [c for c in Z.ASSERTED if Z.expect(c).dirty]
 NLANES = max(len(_mixed()), 64 * len(UNIFORM))
 
 
@@ -109,7 +108,7 @@ def check(got, lanes, what):
     for i, (c, salt) in enumerate(lanes):
         if (c.name, salt) not in want:
             want[c.name, salt] = Z.expect(c, salt)
-        if d := diff(got[i], want[c.name, salt]):
+        if d := Z.diff(got[i], want[c.name, salt]):
             bad.append((i, c.name, salt, d))
     assert not bad, f"{what}: {len(bad)}/{len(lanes)} lanes differ from the model; first: {bad[:4]}"
 
@@ -192,7 +191,7 @@ def test_host_translate_and_read(eng):
     sp, _, _ = Z.zoo()
     eng.restore(0, 64)
     bad = []
-    for va in _host_addresses():
+    for va in Z.host_addresses():
         want = M.host_translate(sp.pages, sp.cr3, va)
         if eng.translate(0, va) != want:
             bad.append((hex(va), eng.translate(0, va), want))
@@ -217,14 +216,14 @@ def test_host_writes(eng, block):
     sp, r0, _ = Z.zoo()
     pfns, blob = sp.phys()
     o = Oracle(pfns=pfns, blob=blob)
-    n = len(HOST_WRITES)
+    n = len(Z.HOST_WRITES)
     eng.restore(0, 64)
     if block:   # every write on 8 lanes at once: lane 8 * w + j
-        recs = [(8 * w + j, va, bytes(range(0xC1 + j, 0xC1 + j + k))) for w, (_, va, k, _) in enumerate(HOST_WRITES)
+        recs = [(8 * w + j, va, bytes(range(0xC1 + j, 0xC1 + j + k))) for w, (_, va, k, _) in enumerate(Z.HOST_WRITES)
                 for j in range(8)]
         st = eng.apply_writes(recs, check=False)
-        assert [s == 0 for s in st] == [HOST_WRITES[r[0] // 8][3] for r in recs]
-    for w, (name, va, k, lands) in enumerate(HOST_WRITES):
+        assert [s == 0 for s in st] == [Z.HOST_WRITES[r[0] // 8][3] for r in recs]
+    for w, (name, va, k, lands) in enumerate(Z.HOST_WRITES):
         for j in range(8 if block else 1):
             lane = 8 * w + j
             data = bytes(range(0xC1 + j, 0xC1 + j + k))
@@ -255,7 +254,7 @@ def test_host_edit_of_a_table_is_seen_after_resume(eng):
     repoints the page's PTE (write_virt on one lane, apply_writes on the
     others); resumed, the second load reads the other frame."""
     sp, _, f = Z.zoo()
-    case = next(c for c in ASSERTED if c.name == "h-two-loads")
+    case = next(c for c in Z.ASSERTED if c.name == "h-two-loads")
     lanes = [(case, 0)] * 64
     bp = Z.entry_rip(case) + 3
     eng.set_breakpoints([bp])
@@ -285,9 +284,7 @@ def test_translate_matches_the_reference_lines():
     from wtf_amd.engine import Engine
     from wtf_amd.tools.snapshot import user_state
 
-    from tests.test_paging import reference_lines
-
-    sp, want = reference_lines()
+    sp, want = M.reference_lines()
     e = Engine(0)
     try:
         pfns, blob = sp.phys()
@@ -309,7 +306,7 @@ def test_device_feed_into_a_table_is_seen_at_once(eng):
     import ctypes as C
 
     sp, _, f = Z.zoo()
-    case = next(c for c in ASSERTED if c.name == "h-two-loads")
+    case = next(c for c in Z.ASSERTED if c.name == "h-two-loads")
     lanes = [(case, 0)] * 64
     bp = Z.entry_rip(case) + 3
     entry = struct.pack("<Q", f["kd", 4] << 12 | Z.P | Z.RW)

@@ -5,7 +5,6 @@ retired instruction count, all 16 GPRs, RFLAGS, the coverage set (every rip
 executed), the dirty-page set, the algorithmic byte counter and the contents
 of the data window and the stack. Bit-exact.
 """
-import numpy as np
 import pytest
 
 from tests import progfuzz
@@ -14,33 +13,12 @@ from wtf_amd.abi import EXIT_FAULT, EXIT_UNIMPLEMENTED, regs_from_state
 pytestmark = pytest.mark.gpu
 
 
-def run_gpu(sp, st, lanes, limit=20000, overlay_pages=8):
-    from wtf_amd.engine import Engine
-
-    n = len(lanes)
-    eng = Engine(0)
-    pfns, blob = sp.phys()
-    eng.load_pool(pfns, blob)
-    eng.alloc_lanes(n, overlay_pages=overlay_pages, cov_entries=4096)
-    eng.set_initial_state(regs_from_state(st))
-    eng.set_limit(limit)
-    eng.restore()
-    g = eng.read_gprs()
-    for i, (va, regs, flags) in enumerate(lanes):
-        g[i, :16] = np.array(regs, dtype=np.uint64)
-        g[i, 16] = va
-        g[i, 17] = flags
-    eng.write_gprs(g)
-    stats = eng.run()
-    return eng, stats
-
-
 @pytest.mark.parametrize("seed", [11, 12, 13])
 def test_gpu_matches_oracle_on_random_programs(seed):
     n = 512
     sp, st, lanes = progfuzz.build(n, seed=seed)
     want = progfuzz.oracle_run(sp, st, lanes)
-    eng, stats = run_gpu(sp, st, lanes)
+    eng, stats = progfuzz.run_gpu(sp, st, lanes)
     ex = eng.exits()
     g = eng.read_gprs()
     cov, ovf = eng.coverage()

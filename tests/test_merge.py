@@ -21,7 +21,6 @@ import pytest
 
 from tests import tlv_harness as H
 from tests.cpu_bins import ALT, HOSTCHECK
-from tests.test_shard_twin import _free_port, _fuzz_cmd, _last_json
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -96,11 +95,11 @@ def _campaign(base, tmp, tag, extra=(), env=None, runs=2048, lanes=256, split=Fa
                 if i % 2 != r:
                     os.remove(os.path.join(d, "inputs", name))
         dirs.append(d)
-    port = _free_port()
-    procs = [subprocess.Popen(_fuzz_cmd(dirs[r], r, 2, port, runs=runs, lanes=lanes) + list(extra),
+    port = H.free_port()
+    procs = [subprocess.Popen(H.fuzz_cmd(dirs[r], r, 2, port, runs=runs, lanes=lanes) + list(extra),
                               stdout=subprocess.PIPE, text=True, env={**os.environ, **(env or {})})
              for r in range(2)]
-    res = [_last_json(p.communicate(timeout=300)[0]) for p in procs]
+    res = [H.last_json(p.communicate(timeout=300)[0]) for p in procs]
     assert all(p.returncode == 0 for p in procs)
     files = [(sorted(os.listdir(os.path.join(d, "outputs"))), sorted(os.listdir(os.path.join(d, "crashes"))))
              for d in dirs]

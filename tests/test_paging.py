@@ -17,15 +17,13 @@ import struct
 
 import pytest
 
-from wtf_amd.abi import Regs
-
 from tests import paging_cases as Z
 from tests import paging_model as M
+from tests import simlane
 from tests.oracle_lib import Oracle
-from tests.test_sys2 import SimResult, sim_lib
 
 LIMIT = 1000
-ASSERTED = [c for c in Z.cases() if c.family != "link-unasserted"]
+ASSERTED, HOST_WRITES, diff = Z.ASSERTED, Z.HOST_WRITES, Z.diff
 
 
 # ---------------------------------------------------------------- the three engines
@@ -61,49 +59,20 @@ def run_oracle(o, case, salt=0):
 @pytest.fixture(scope="module")
 def sim():
     sp, _, _ = Z.zoo()
-    pfns, blob = sp.phys()
-    return sim_lib(), (C.c_uint64 * len(pfns))(*pfns), blob, len(pfns)
+    return simlane.image(sp)
 
 
 def run_sim(sim, case, fast, salt=0):
-    L, arr, blob, n = sim
-    res, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
-    pages = C.create_string_buffer(64 * 4096)
+    pages = simlane.page_buffer()
     r = Z.lane_regs(case, salt)
     win = case.ops[-1][1]
-    L.sim_run_full(arr, blob, n, C.byref(r), LIMIT, C.byref(res), fast, C.byref(cnt), win, C.byref(fin), pages)
+    res, fin, cnt = simlane.run(sim, r, limit=LIMIT, fast=fast, win_va=win, pages=pages)
     k = min(res.ovn, 64)
     dirty = [int(res.dirty[i]) >> 12 for i in range(k)]
     return {"status": res.status, "vector": res.vector, "error": res.error, "addr": res.addr, "rip": res.rip,
             "icount": res.icount, "gpr": list(res.gpr), "vec": _vecs(fin), "dirty": sorted(dirty),
             "mem": {p: pages.raw[i * 4096:(i + 1) * 4096] for i, p in enumerate(dirty)},
-            "views": {win: bytes(res.win[:8])}, "fast": cnt.value}
-
-
-def diff(got, want):
-    """The fields in which an engine's result differs from the model's."""
-    bad = []
-    if got["status"] != want.status:
-        bad.append(("status", got["status"], want.status))
-    elif want.status == Z.EXIT_FAULT:
-        if (got["vector"], got["error"]) != (want.vector, want.error):
-            bad.append(("fault", got["vector"], got["error"], want.vector, want.error))
-        if want.addr is not None and got["addr"] != want.addr:
-            bad.append(("addr", hex(got["addr"]), hex(want.addr)))
-    for k in ("rip", "icount"):
-        if got[k] != getattr(want, k):
-            bad.append((k, got[k], getattr(want, k)))
-    bad += [("gpr", r, hex(got["gpr"][r]), hex(v)) for r, v in want.gpr.items() if got["gpr"][r] != v]
-    bad += [("vec", i) for i, b in want.vec.items() if got["vec"][i][:len(b)] != b]
-    if got["dirty"] != want.dirty:
-        bad.append(("dirty", [hex(p) for p in got["dirty"]], [hex(p) for p in want.dirty]))
-    elif got["mem"] != want.mem:
-        bad.append(("mem", [hex(p) for p in want.dirty if got["mem"][p] != want.mem[p]]))
-    for va, b in got["views"].items():
-        # (the host build's window is the guest's walk from ring 0, byte by byte: compared where all 8 bytes translate)
-        if b != want.views[va] and not ("fast" in got and (want.views[va] is None or not M.canonical(va))):
-            bad.append(("view", hex(va), b, want.views[va]))
-    return bad
+            "views": {win: bytes(res.win[:8])}, "fast": cnt}
 
 
 def _report(bad):
@@ -239,27 +208,13 @@ def test_runtime_linked_table_without_invlpg_is_recorded(oracle, sim):
 
 
 # ---------------------------------------------------------------- host accesses
-def _host_addresses():
-    vas = {va for c in Z.cases() for _, va, _ in c.ops}
-    vas |= {Z.U1G + Z.GIB - 1, Z.L2 + Z.MIB2 - 1, Z.L2 + Z.MIB2, Z.HOLE, Z.HOLE - 1, Z.L2_U0, Z.L2_NX + 0x1234, Z.L2_W0 + 7,
-            Z.U1G_U0 + 0x2FFFFFFF, Z.PTWIN, Z.LWIN + 0x1FFFFF, Z.KLEAF + 0x3000, Z.KLINK, 0, 0xFFFF800000000000}
-    return sorted(vas)
-
-
 def test_host_translate_is_present_bits_only(oracle):
     sp, r0, _ = Z.zoo()
     oracle.restore(r0)
-    bad = [(hex(va), oracle.translate(va), M.host_translate(sp.pages, sp.cr3, va)) for va in _host_addresses()
+    bad = [(hex(va), oracle.translate(va), M.host_translate(sp.pages, sp.cr3, va)) for va in Z.host_addresses()
            if oracle.translate(va) != M.host_translate(sp.pages, sp.cr3, va)]
     assert not bad, bad[:5]
-    assert sum(M.host_translate(sp.pages, sp.cr3, va) is None for va in _host_addresses()) >= 4
-
-
-HOST_WRITES = [  # (name, va, bytes written, lands)
-    ("ro-2m-leaf", Z.L2_W0 + 0x1FFC, 8, True), ("ro-1g-leaf", Z.U1G_W0 + Z.GIB - 8, 8, True),
-    ("supervisor-nx-4k", Z.PLACE["U0", 1] + 0xFF0, 16, True), ("absent-frame", Z.L2 + Z.MIB2 // 2 + 4, 8, True),
-    ("out-of-leaf-into-hole", Z.L2_B + Z.MIB2 - 4, 8, False), ("hole", Z.HOLE + 8, 8, False),
-]
+    assert sum(M.host_translate(sp.pages, sp.cr3, va) is None for va in Z.host_addresses()) >= 4
 
 
 @pytest.mark.parametrize("name,va,n,lands", HOST_WRITES, ids=[w[0] for w in HOST_WRITES])
@@ -284,42 +239,18 @@ def test_host_write_virt(oracle, name, va, n, lands):
 
 
 # ---------------------------------------------------------------- the reference's own walk
-def reference_lines():
-    """The large-page dump of tests/test_snapshot_format.py and what the
-    reference's kdmp-parser translates its addresses to (the committed VT lines
-    of tests/golden/kdmp_fixtures.json): (AddressSpace, {gva: gpa or None}).
-    In a leaf with PAT set kdmp-parser adds bit 12 of the entry into the
-    address; there the SDM's address (tables 4-15, 4-17) is what is wanted."""
-    import json
-
-    from tests import test_snapshot_format as F
-
-    sp, gvas = F.large_page_space()
-    ref = F.vt(json.load(open(F.FIXTURES))["large_full"])
-    assert set(ref) == set(gvas) and len(ref) >= 40
-    want = {}
-    for g in gvas:
-        model = M.host_translate(sp.pages, sp.cr3, g)
-        assert model == (ref[g] - 0x1000 if F.in_pat_leaf(g) else ref[g]), hex(g)   # the model against the reference
-        want[g] = model
-    assert sum(v is None for v in want.values()) >= 6 and sum(map(F.in_pat_leaf, gvas)) == 8
-    return sp, want
-
-
 def test_walks_match_the_reference_lines(sim):
     from wtf_amd.abi import regs_from_state
     from wtf_amd.tools.snapshot import user_state
 
-    sp, want = reference_lines()
+    sp, want = M.reference_lines()
     pfns, blob = sp.phys()
     o = Oracle(pfns=pfns, blob=blob)
     o.restore(regs_from_state(user_state(0x140000000, 0x7F8000000100, sp.cr3)))
-    L = sim[0]
-    L.sim_translate.argtypes = [C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     arr = (C.c_uint64 * len(pfns))(*pfns)
     for g, gpa in want.items():
         assert o.translate(g) == gpa, hex(g)
         out = C.c_uint64()
-        rc = L.sim_translate(arr, blob, len(pfns), sp.cr3, g, C.byref(out))
+        rc = simlane.lib().sim_translate(arr, blob, len(pfns), sp.cr3, g, C.byref(out))
         if M.canonical(g):   # (the device walk refuses a non-canonical address; the host's takes its low 48 bits)
             assert (None if rc else out.value) == gpa, hex(g)

@@ -9,10 +9,8 @@ through the node's CoverageExchange_t (TCP on the CPU, net_exchange.cc).
     testcases in its corpus;
   * the union is at least what either shard alone covers.
 """
-import json
 import os
 import shutil
-import socket
 import subprocess
 
 import pytest
@@ -20,24 +18,6 @@ import pytest
 from tests import tlv_harness as H
 
 pytestmark = pytest.mark.skipif(not os.path.exists(H.TWIN), reason="oracle/wtf_twin not built")
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _fuzz_cmd(d, rank, world, port, runs=3072, lanes=512):
-    return [H.TWIN, "fuzz", "--name", "tlv_server", "--target", d, "--runs", str(runs), "--lanes", str(lanes),
-            "--seed", "1337", "--limit", "100000", "--rank", str(rank), "--world", str(world),
-            "--exchange", f"127.0.0.1:{port}"]
-
-
-def _last_json(out):
-    return json.loads([x for x in out.splitlines() if x.startswith("{")][-1])
 
 
 @pytest.fixture(scope="module")
@@ -57,9 +37,9 @@ def test_two_twin_shards_merge_coverage(base, tmp_path):
             if i % 2 != r:
                 os.remove(os.path.join(d, "inputs", name))
         dirs.append(d)
-    port = _free_port()
-    procs = [subprocess.Popen(_fuzz_cmd(dirs[r], r, 2, port), stdout=subprocess.PIPE, text=True) for r in range(2)]
-    res = [_last_json(p.communicate(timeout=300)[0]) for p in procs]
+    port = H.free_port()
+    procs = [subprocess.Popen(H.fuzz_cmd(dirs[r], r, 2, port), stdout=subprocess.PIPE, text=True) for r in range(2)]
+    res = [H.last_json(p.communicate(timeout=300)[0]) for p in procs]
     assert all(p.returncode == 0 for p in procs)
     assert [r["rank"] for r in res] == [0, 1] and all(r["world"] == 2 for r in res)
     assert res[0]["coverage"] == res[1]["coverage"]
@@ -72,8 +52,8 @@ def test_two_twin_shards_merge_coverage(base, tmp_path):
     # one shard alone (same seed as rank 0) covers no more than the union
     solo = str(tmp_path / "solo")
     shutil.copytree(base, solo, ignore=shutil.ignore_patterns("outputs", "crashes", "work"))
-    one = subprocess.run(_fuzz_cmd(solo, 0, 1, port), capture_output=True, text=True, timeout=300, check=True)
-    assert _last_json(one.stdout)["coverage"] <= res[0]["coverage"]
+    one = subprocess.run(H.fuzz_cmd(solo, 0, 1, port), capture_output=True, text=True, timeout=300, check=True)
+    assert H.last_json(one.stdout)["coverage"] <= res[0]["coverage"]
 
 
 def test_two_twin_shards_merge_edges_outside_the_map(base, tmp_path):
@@ -86,18 +66,18 @@ def test_two_twin_shards_merge_edges_outside_the_map(base, tmp_path):
         d = str(tmp_path / f"e{r}")
         shutil.copytree(base, d, ignore=shutil.ignore_patterns("outputs", "crashes", "work"))
         dirs.append(d)
-    port = _free_port()
-    procs = [subprocess.Popen(_fuzz_cmd(dirs[r], r, 2, port, runs=2048) + ["--edges", "--seed", str(1337 + r)],
+    port = H.free_port()
+    procs = [subprocess.Popen(H.fuzz_cmd(dirs[r], r, 2, port, runs=2048) + ["--edges", "--seed", str(1337 + r)],
                               stdout=subprocess.PIPE, text=True) for r in range(2)]
-    res = [_last_json(p.communicate(timeout=300)[0]) for p in procs]
+    res = [H.last_json(p.communicate(timeout=300)[0]) for p in procs]
     assert all(p.returncode == 0 for p in procs)
     assert res[0]["coverage"] == res[1]["coverage"]
     # edges make the aggregate larger than the rips alone
     solo = str(tmp_path / "solo_noedges")
     shutil.copytree(base, solo, ignore=shutil.ignore_patterns("outputs", "crashes", "work"))
-    one = subprocess.run(_fuzz_cmd(solo, 0, 1, port, runs=2048), capture_output=True, text=True, timeout=300,
+    one = subprocess.run(H.fuzz_cmd(solo, 0, 1, port, runs=2048), capture_output=True, text=True, timeout=300,
                          check=True)
-    assert res[0]["coverage"] > _last_json(one.stdout)["coverage"]
+    assert res[0]["coverage"] > H.last_json(one.stdout)["coverage"]
 
 
 def test_shards_stopping_at_different_times(base, tmp_path):
@@ -109,9 +89,9 @@ def test_shards_stopping_at_different_times(base, tmp_path):
         d = str(tmp_path / f"t{r}")
         shutil.copytree(base, d, ignore=shutil.ignore_patterns("outputs", "crashes", "work"))
         dirs.append(d)
-    port = _free_port()
-    cmds = [_fuzz_cmd(dirs[r], r, 2, port, runs=0, lanes=64) + ["--seconds", str(1.0 + 2.0 * r)] for r in range(2)]
+    port = H.free_port()
+    cmds = [H.fuzz_cmd(dirs[r], r, 2, port, runs=0, lanes=64) + ["--seconds", str(1.0 + 2.0 * r)] for r in range(2)]
     procs = [subprocess.Popen(c, stdout=subprocess.PIPE, text=True) for c in cmds]
-    res = [_last_json(p.communicate(timeout=120)[0]) for p in procs]
+    res = [H.last_json(p.communicate(timeout=120)[0]) for p in procs]
     assert all(p.returncode == 0 for p in procs)
     assert res[0]["coverage"] == res[1]["coverage"]

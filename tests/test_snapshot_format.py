@@ -24,7 +24,6 @@ from __future__ import annotations
 
 import json
 import os
-import struct
 import subprocess
 import sys
 import tempfile
@@ -37,8 +36,8 @@ sys.path.insert(0, ROOT)
 from wtf_amd.tools import snapshot, syn  # noqa: E402
 
 from tests.cpu_bins import ALT, HOSTCHECK as TOOL  # noqa: E402
+from tests.paging_model import FIXTURES, in_pat_leaf, large_page_space, vt  # noqa: E402
 REF = os.path.join(ROOT, "oracle", "_ref", "kdmp_ref")
-FIXTURES = os.path.join(ROOT, "tests", "golden", "kdmp_fixtures.json")
 PREFIXES = ("TYPE ", "CR3 ", "RIP ", "PAGE ", "VT ", "PARSE_FAIL")
 
 
@@ -61,52 +60,6 @@ def ours(dump: str, gvas: list[int]) -> list[str]:
 def reference(dump: str, gvas: list[int]) -> list[str]:
     r = subprocess.run([REF, dump, *map(hex, gvas)], capture_output=True, text=True)
     return lines(r.stdout)
-
-
-PAT_1G, PAT_2M = 6, 12   # the PDPT / PD slots of the PAT leaves
-
-
-def in_pat_leaf(gva: int) -> bool:
-    return 0x7F8000000000 + (PAT_1G << 30) <= gva < 0x7F8000000000 + (PAT_1G + 1 << 30) or \
-        0x7F8040000000 + (PAT_2M << 21) <= gva < 0x7F8040000000 + (PAT_2M + 1 << 21)
-
-
-def vt(out: list[str]) -> dict[int, int | None]:
-    """{gva: gpa or None} of the VT lines."""
-    return {int(a, 16): None if b == "-1" else int(b, 16) for a, b in (ln.split()[1:] for ln in out if ln.startswith("VT "))}
-
-
-def large_page_space():
-    """Page tables with a 1 GiB leaf (PDPTE.PS) and a 2 MiB leaf (PDE.PS),
-    the kdmp-parser walk's large-page branches (kdmp-parser.h:300-330)."""
-    sp = snapshot.AddressSpace()
-    sp.map(0x140000000, b"\x90" * 16)               # an ordinary 4 KiB page
-    pml4 = sp.cr3 >> 12
-    # 1 GiB leaf at 0x7f8000000000 -> gpa 0x40000000
-    pdpt = sp.alloc()
-    struct.pack_into("<Q", sp.pages[pml4], 0xFF * 8, (pdpt << 12) | 0x7)
-    struct.pack_into("<Q", sp.pages[pdpt], 0, 0x40000000 | 0x87)
-    # 2 MiB leaf at 0x7f8040000000 -> gpa 0x200000
-    pd = sp.alloc()
-    struct.pack_into("<Q", sp.pages[pdpt], 1 * 8, (pd << 12) | 0x7)
-    struct.pack_into("<Q", sp.pages[pd], 3 * 8, 0x200000 | 0x87)
-    # the same frames again through leaves that carry the bits a walk must ignore (G, A, D, the software
-    # bits 9-11 and 52-62), through W = 0, U = 0 and NX leaves, and through leaves with PAT (bit 12 of a
-    # large leaf) set
-    ign = 0x100 | 0x20 | 0x40 | 0xE00 | (0x7FF << 52)
-    for i, bits in ((2, 0x87 | ign), (3, 0x85), (4, 0x83), (5, 0x87 | 1 << 63), (PAT_1G, 0x87 | 0x1000)):
-        struct.pack_into("<Q", sp.pages[pdpt], i * 8, 0x40000000 | bits)
-    for i, bits in ((5, 0x87 | ign), (9, 0x85), (10, 0x83), (11, 0x87 | 1 << 63), (PAT_2M, 0x87 | 0x1000)):
-        struct.pack_into("<Q", sp.pages[pd], i * 8, 0x200000 | bits)
-    # a few pages inside both large mappings, so GetPhysicalPage sees them
-    for gpa in (0x40000000, 0x40001000, 0x200000, 0x3FF000):
-        sp.pages[gpa >> 12] = bytearray(struct.pack("<Q", gpa) * 512)
-    gvas = [0x140000000, 0x140000FFF, 0x7F8000000000, 0x7F8000001234, 0x7F803FFFFFFF, 0x7F8040600000,
-            0x7F80407FFFFF, 0x7F8040800000, 0x7F9000000000, 0x0, 0xFFFF800000000000, 0x800000000000]
-    for base, size in [(0x7F8000000000 + (i << 30), 1 << 30) for i in (2, 3, 4, 5, PAT_1G)] + \
-                      [(0x7F8040000000 + (i << 21), 1 << 21) for i in (5, 9, 10, 11, PAT_2M)]:
-        gvas += [base, base + 0x1234, base + size - 1, base + size]   # first, inside, last byte, first byte past the end
-    return sp, gvas
 
 
 def syn_space():

@@ -7,107 +7,20 @@ cannot show without crashing (misaligned 16-byte operands, CR0/CR4 gating,
 register-only / memory-only encodings) is checked by hand here; the GPU engine
 is compared with the oracle on all of it in test_gpu_sse.py.
 """
-import gzip
-import json
-import os
-
 import pytest
 
-from tests.golden.gen_native_vectors import splitmix_bytes
-from tests.golden.gen_sse_vectors import window_in
-from tests.oracle_lib import Oracle
-from wtf_amd.abi import EXIT_FAULT, EXIT_UNIMPLEMENTED, RUNNING, regs_from_state
-from wtf_amd.tools.snapshot import AddressSpace, user_state
+from tests import simlane
+from tests.insn_cases import BUF, SSE_FAULT_CASES, build, layout
+from tests.vector_replay import SSE, replay_oracle, replay_sim, run_family
+from wtf_amd.abi import EXIT_FAULT, RUNNING, regs_from_state
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CODE_VA = 0x140001000
-
-
-def load():
-    with gzip.open(os.path.join(HERE, "golden", "sse_vectors.json.gz"), "rt") as f:
-        return json.load(f)
-
-
-DOC = load()
-
-
-def case_regs(case, regs):
-    for i in range(16):
-        regs.gpr[i] = int(case["in"][i], 16)
-    regs.rflags = int(case["fl"], 16) | 0x200
-    xs = [int(v, 16) for v in case["xin"]]
-    for i in range(16):
-        regs.xmm[i][0], regs.xmm[i][1] = xs[2 * i], xs[2 * i + 1]
-    regs.mxcsr = int(case["mx"], 16)
-    return regs
-
-
-def layout(code: bytes, buf_va, window: bytes, cr0=None, cr4=None):
-    """The address space of one case (code page, window page + the next page)
-    and its initial registers."""
-    page_va = buf_va & ~0xFFF
-    sp = AddressSpace()
-    sp.map(CODE_VA, code + b"\xcc", write=False)
-    first = bytearray(4096)
-    off = buf_va - page_va
-    first[off:off + len(window)] = window
-    sp.map(page_va, bytes(first))
-    sp.map(page_va + 0x1000, b"")
-    regs = regs_from_state(user_state(CODE_VA, 0, sp.cr3))
-    if cr0 is not None:
-        regs.cr0 = cr0
-    if cr4 is not None:
-        regs.cr4 = cr4
-    return sp, regs
-
-
-def build(code: bytes, buf_va, window: bytes, cr0=None, cr4=None):
-    sp, regs = layout(code, buf_va, window, cr0, cr4)
-    pfns, blob = sp.phys()
-    return Oracle(pfns=pfns, blob=blob), regs
-
-
-def check_case(c, buf_va, o, r):
-    """Mismatch description, or None."""
-    want = [int(x, 16) for x in c["out"]]
-    if list(r.gpr) != want:
-        return ("regs", [(i, hex(r.gpr[i]), hex(want[i])) for i in range(16) if r.gpr[i] != want[i]])
-    if (r.rflags ^ int(c["flo"], 16)) & 0x8D5:
-        return ("flags", hex(r.rflags), c["flo"])
-    xo = [int(v, 16) for v in c["xout"]]
-    got = [r.xmm[i][h] for i in range(16) for h in range(2)]
-    if got != xo:
-        return ("xmm", [(i // 2, hex(got[i]), hex(xo[i])) for i in range(32) if got[i] != xo[i]])
-    if r.mxcsr != int(c["mxo"], 16):
-        return ("mxcsr", hex(r.mxcsr), c["mxo"])
-    return None
+DOC = SSE.doc
 
 
 @pytest.mark.parametrize("chunk", range(4))
 def test_oracle_matches_native_sse(chunk):
-    buf_va = int(DOC["buf_va"], 16)
     cases = DOC["cases"][chunk::4]
-    fails = []
-    for c in cases:
-        o, regs = build(bytes.fromhex(c["code"]), buf_va, window_in(int(c["seed"], 16), c["ldmx"]))
-        o.restore(case_regs(c, regs))
-        ex = o.step()
-        if ex.status != RUNNING:
-            fails.append((c["name"], c["code"], "exit", ex.status, ex.vector))
-            continue
-        r = o.regs()
-        bad = check_case(c, buf_va, o, r)
-        if bad:
-            fails.append((c["name"], c["code"]) + bad)
-            continue
-        win = bytearray(window_in(int(c["seed"], 16), c["ldmx"]))
-        for i, v in c["diff"]:
-            win[i] = v
-        if o.read_virt(buf_va, 256) != bytes(win):
-            fails.append((c["name"], c["code"], "mem"))
-            continue
-        if r.rip != CODE_VA + len(bytes.fromhex(c["code"])):
-            fails.append((c["name"], c["code"], "rip"))
+    fails = run_family(SSE, replay_oracle, cases)
     assert not fails, f"{len(fails)}/{len(cases)} mismatches, first: {fails[:6]}"
 
 
@@ -119,9 +32,6 @@ def test_sse_vector_file_is_substantial():
 
 
 # ---- hand-checked faults and encodings (what native execution cannot show)
-BUF = 0x7FF000100800  # any user address: these cases do not use the native window
-
-
 def run1(code, regs_fn=None, cr0=None, cr4=None):
     o, regs = build(bytes(code), BUF, bytes(range(256)), cr0=cr0, cr4=cr4)
     regs.gpr[3] = BUF + 0x10  # rbx -> window + 16 (16-byte aligned)
@@ -130,27 +40,6 @@ def run1(code, regs_fn=None, cr0=None, cr4=None):
         regs_fn(regs)
     o.restore(regs)
     return o, o.step()
-
-
-SSE_FAULT_CASES = [
-    # (bytes, expected status, vector)
-    ([0x0F, 0x28, 0x06], EXIT_FAULT, 13),             # movaps xmm0, [rsi] misaligned -> #GP(0)
-    ([0x66, 0x0F, 0xEF, 0x06], EXIT_FAULT, 13),       # pxor xmm0, [rsi] misaligned
-    ([0x66, 0x0F, 0x7F, 0x06], EXIT_FAULT, 13),       # movdqa [rsi], xmm0 misaligned
-    ([0xF3, 0x0F, 0x6F, 0x06], RUNNING, None),        # movdqu xmm0, [rsi]: fine
-    ([0x0F, 0x11, 0x06], RUNNING, None),              # movups [rsi], xmm0: fine
-    ([0x0F, 0x28, 0x03], RUNNING, None),              # movaps xmm0, [rbx] aligned
-    ([0x66, 0x0F, 0xD7, 0x03], EXIT_FAULT, 6),        # pmovmskb eax, [rbx]: register-only -> #UD
-    ([0x66, 0x0F, 0x73, 0x1B, 0x04], EXIT_FAULT, 6),  # psrldq [rbx], 4: register-only
-    ([0x0F, 0x13, 0xC1], EXIT_FAULT, 6),              # movlps xmm1, xmm0 (0f 13 reg): #UD
-    ([0x0F, 0x2B, 0xC1], EXIT_FAULT, 6),              # movntps reg form: #UD
-    ([0x0F, 0xC3, 0xC1], EXIT_FAULT, 6),              # movnti reg form: #UD
-    ([0x0F, 0xEF, 0xC1], RUNNING, None),              # MMX pxor mm0, mm1 (U37)
-    ([0x0F, 0xF7, 0xC1], RUNNING, None),              # MMX maskmovq (no byte selected: nothing written)
-    ([0x0F, 0x58, 0xC1], RUNNING, None),              # addps (floating point, U39)
-    ([0xF2, 0x0F, 0xF0, 0x03], RUNNING, None),        # lddqu (SSE3, U39)
-    ([0x0F, 0x53, 0xC1], RUNNING, None),              # rcpps (the host CPU's table, U40)
-]
 
 
 @pytest.mark.parametrize("code,status,vector", SSE_FAULT_CASES)
@@ -197,63 +86,17 @@ def test_oracle_page_crossing_movdqu_store_faults_whole():
 # (tests/native/sim_lane.cc: one lane of k_run's decode / exec / retry loop)
 # against the native vectors and the oracle, so the device semantics are
 # checked on CPU before any GPU run.
-import ctypes as C  # noqa: E402
-
-from tests.cpu_bins import SIMLANE_SO, ensure  # noqa: E402
-from wtf_amd.abi import Regs  # noqa: E402
-
-
-class SimResult(C.Structure):
-    _fields_ = [("gpr", C.c_uint64 * 16), ("rip", C.c_uint64), ("rflags", C.c_uint64), ("icount", C.c_uint64),
-                ("nbytes", C.c_uint64), ("status", C.c_uint32), ("vector", C.c_uint32), ("error", C.c_uint32),
-                ("ovn", C.c_uint32), ("addr", C.c_uint64), ("dirty", C.c_uint64 * 64), ("xmm", C.c_uint64 * 32),
-                ("mxcsr", C.c_uint32), ("pad", C.c_uint32), ("ymmh", C.c_uint64 * 32), ("win", C.c_uint8 * 512)]
-
-
-def sim_lib():
-    L = C.CDLL(ensure(SIMLANE_SO, os.path.join(HERE, "native")))
-    L.sim_run.argtypes = [C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64, C.POINTER(Regs), C.c_uint64,
-                          C.POINTER(SimResult)]
-    L.sim_run_mode.argtypes = L.sim_run.argtypes + [C.c_int, C.POINTER(C.c_uint64), C.c_uint64]
-    return L
-
-
-def sim_run(L, sp, regs, limit=0, fast=False, counter=None, win_va=0):
-    """One lane from `regs` until it stops; fast=True tries the fast loop's
-    form of each instruction first (k_run's order). `counter` (a c_uint64)
-    counts the instructions the fast form retired; `win_va` selects the 512
-    bytes returned in `win`."""
-    pfns, blob = sp.phys()
-    arr = (C.c_uint64 * len(pfns))(*pfns)
-    out = SimResult()
-    cnt = counter if counter is not None else C.c_uint64(0)
-    L.sim_run_mode(arr, blob, len(pfns), C.byref(regs), limit, C.byref(out), 1 if fast else 0, C.byref(cnt), win_va)
-    return out
-
-
 def test_engine_sse_code_matches_native_vectors():
-    L = sim_lib()
-    buf_va = int(DOC["buf_va"], 16)
-    fails = []
-    for c in DOC["cases"]:
-        sp, regs = layout(bytes.fromhex(c["code"]), buf_va, window_in(int(c["seed"], 16), c["ldmx"]))
-        out = sim_run(L, sp, case_regs(c, regs))
-        if out.status != 3 or out.icount != 1:  # int3 after the instruction
-            fails.append((c["name"], c["code"], "exit", out.status, out.vector))
-        elif list(out.gpr) != [int(x, 16) for x in c["out"]] or (out.rflags ^ int(c["flo"], 16)) & 0x8D5:
-            fails.append((c["name"], c["code"], "regs"))
-        elif list(out.xmm) != [int(v, 16) for v in c["xout"]] or out.mxcsr != int(c["mxo"], 16):
-            fails.append((c["name"], c["code"], "xmm"))
+    fails = run_family(SSE, replay_sim, DOC["cases"])
     assert not fails, f"{len(fails)}/{len(DOC['cases'])} mismatches, first: {fails[:6]}"
 
 
 @pytest.mark.parametrize("code,status,vector", SSE_FAULT_CASES)
 def test_engine_sse_code_faults(code, status, vector):
-    L = sim_lib()
     sp, regs = layout(bytes(code), BUF, bytes(range(256)))
     regs.gpr[3] = BUF + 0x10
     regs.gpr[6] = BUF + 0x13
-    out = sim_run(L, sp, regs)
+    out, _, _ = simlane.run(sp, regs)
     want = 3 if status == RUNNING else status  # a clean run stops at the int3
     assert out.status == want, (bytes(code).hex(), out.status, out.vector)
     if vector is not None:
@@ -265,7 +108,6 @@ def test_engine_sse_code_matches_oracle_on_random_programs(fast, fp):
     """fp: with the floating-point and SSE4 / AVX2 forms and a random MXCSR per lane."""
     from tests import progfuzz
 
-    L = sim_lib()
     n = 160
     seed = 33 if fp else 31
     sp, st, lanes = progfuzz.build(n, seed=seed, sse=True, fp=fp)
@@ -273,6 +115,7 @@ def test_engine_sse_code_matches_oracle_on_random_programs(fast, fp):
     ymmh = progfuzz.lane_xmm(n, seed, 0x4E4)
     mx = progfuzz.lane_mxcsr(n, seed) if fp else None
     want = progfuzz.oracle_run(sp, st, lanes, xmm=xmm, ymmh=ymmh, mxcsr=mx)
+    img = simlane.image(sp)
     bad = []
     for i, ((va, g, flags), w) in enumerate(zip(lanes, want)):
         regs = regs_from_state(st)
@@ -283,7 +126,7 @@ def test_engine_sse_code_matches_oracle_on_random_programs(fast, fp):
         regs.rip, regs.rflags = va, flags
         if mx is not None:
             regs.mxcsr = mx[i]
-        out = sim_run(L, sp, regs, limit=20000, fast=fast)
+        out, _, _ = simlane.run(img, regs, limit=20000, fast=fast)
         got = (out.status, out.vector if out.status == EXIT_FAULT else 0, out.rip, out.icount)
         exp = (w["status"], w["vector"] if w["status"] == EXIT_FAULT else 0, w["rip"], w["icount"])
         if got != exp:

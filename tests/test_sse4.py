@@ -7,87 +7,24 @@ checks and memory access) and the engine's device code built for the host;
 the GPU runs them in tests/test_gpu_sse.py. Hand-checked: the #UD rules
 (VEX.L, VEX.W, vvvv, memory-only forms) and alignment.
 """
-import gzip
-import json
-import os
-
 import pytest
 
-from tests.golden.gen_sse4_vectors import case_inputs
-from tests.oracle_lib import Oracle
-from tests.test_avx import get_ymm, set_ymm
-from tests.test_fp import check, norm, run_case
-from tests.test_sse import layout, sim_lib, sim_run
+from tests.insn_cases import norm, run_case
+from tests.vector_replay import SSE4, replay_oracle, replay_sim, run_family
 from wtf_amd.abi import EXIT_FAULT, RUNNING
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def load():
-    with gzip.open(os.path.join(HERE, "golden", "sse4_vectors.json.gz"), "rt") as f:
-        return json.load(f)
-
-
-DOC = load()
-
-
-def inputs(c):
-    ymm, win = case_inputs(int(c["seed"], 16))
-    return [v for r in ymm for v in r], b"".join(v.to_bytes(8, "little") for v in win)
-
-
-def case_regs(c, regs, yin):
-    for i in range(16):
-        regs.gpr[i] = int(c["in"][i], 16)
-    regs.rflags = int(c["fl"], 16) | 0x200
-    set_ymm(regs, yin)
-    regs.mxcsr = int(c["mx"], 16)
-    return regs
-
-
-def window_after(c, win):
-    w = bytearray(win)
-    for i, v in c["mdiff"]:
-        w[i] = v
-    return bytes(w)
+DOC = SSE4.doc
 
 
 @pytest.mark.parametrize("chunk", range(2))
 def test_oracle_matches_native_sse4(chunk):
-    buf_va = int(DOC["buf_va"], 16)
     cases = DOC["cases"][chunk::2]
-    fails = []
-    for c in cases:
-        yin, win = inputs(c)
-        sp, regs = layout(bytes.fromhex(c["code"]), buf_va, win)
-        pfns, blob = sp.phys()
-        o = Oracle(pfns=pfns, blob=blob)
-        o.restore(case_regs(c, regs, yin))
-        ex = o.step()
-        r = o.regs()
-        ymm = get_ymm([r.xmm[i][h] for i in range(16) for h in range(2)], [r.ymmh[i][h] for i in range(16) for h in range(2)])
-        bad = check(c, ex.status, ex.vector, r.gpr, r.rflags, ymm, r.mxcsr, yin)
-        if not bad and o.read_virt(buf_va, 256) != window_after(c, win):
-            bad = ("mem",)
-        if bad:
-            fails.append((c["name"], c["code"]) + bad)
+    fails = run_family(SSE4, replay_oracle, cases)
     assert not fails, f"{len(fails)}/{len(cases)} mismatches, first: {fails[:5]}"
 
 
 def test_engine_sse4_code_matches_native_vectors():
-    L = sim_lib()
-    buf_va = int(DOC["buf_va"], 16)
-    fails = []
-    for c in DOC["cases"]:
-        yin, win = inputs(c)
-        sp, regs = layout(bytes.fromhex(c["code"]), buf_va, win)
-        out = sim_run(L, sp, case_regs(c, regs, yin), win_va=buf_va)
-        bad = check(c, out.status, out.vector, out.gpr, out.rflags, get_ymm(list(out.xmm), list(out.ymmh)),
-                    out.mxcsr, yin)
-        if not bad and bytes(out.win[:256]) != window_after(c, win):
-            bad = ("mem",)
-        if bad:
-            fails.append((c["name"], c["code"]) + bad)
+    fails = run_family(SSE4, replay_sim, DOC["cases"])
     assert not fails, f"{len(fails)}/{len(DOC['cases'])} mismatches, first: {fails[:5]}"
 
 
@@ -126,8 +63,7 @@ SSE4_FAULT_CASES = [
 
 @pytest.mark.parametrize("code,status,vector", SSE4_FAULT_CASES)
 def test_sse4_faults_oracle_and_engine(code, status, vector):
-    L = sim_lib()
-    for got in (run_case(code), run_case(code, sim=L)):
+    for got in (run_case(code), run_case(code, sim=True)):
         assert norm(got[0]) == status, (bytes(code).hex(), got[:2])
         if vector is not None:
             assert got[1] == vector

@@ -12,7 +12,6 @@ import os
 import pytest
 
 from tests import tlv_harness as H
-from tests.test_stream_twin import _campaign
 
 pytestmark = pytest.mark.skipif(not os.path.exists(H.TWIN), reason="oracle/wtf_twin not built")
 
@@ -22,9 +21,9 @@ LANES, RUNS = 8192, 24576
 def test_wide_streaming_campaign_equals_batch(tmp_path):
     base = H.build_target(str(tmp_path / "base"))
     args = ("tlv_server", RUNS, LANES)
-    a = _campaign(base, str(tmp_path / "batch"), *args, stream=False)
-    b = _campaign(base, str(tmp_path / "stream"), *args, stream=True)
-    c = _campaign(base, str(tmp_path / "serial"), *args, stream=True,
+    a = H.stream_campaign(base, str(tmp_path / "batch"), *args, stream=False)
+    b = H.stream_campaign(base, str(tmp_path / "stream"), *args, stream=True)
+    c = H.stream_campaign(base, str(tmp_path / "serial"), *args, stream=True,
                   extra=("--sample", str(tmp_path / "s.jsonl"), "--sample-every", "997"))
     assert a[0]["execs"] == RUNS
     assert a == b

@@ -5,18 +5,14 @@ engine against the oracle lane by lane (-m gpu). Compared per lane: exit
 (status, vector, error code, cr2, rip, retired count), algorithmic bytes,
 GPRs, RFLAGS, selectors, fs / gs bases, control / x87 / MXCSR / descriptor-
 table state, XMM / YMM registers and the contents of every dirty page."""
-import ctypes as C
-import os
 import struct
 
 import pytest
 
 from tests import sysprog2 as S
-from tests.cpu_bins import SIMLANE_SO, ensure
 from wtf_amd import abi
-from wtf_amd.abi import Regs, regs_from_state
+from wtf_amd.abi import regs_from_state
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 HLT, INT3, FAULT, UNIMPL, TIMEOUT = abi.EXIT_HLT, abi.EXIT_INT3, abi.EXIT_FAULT, abi.EXIT_UNIMPLEMENTED, abi.EXIT_TIMEOUT
 
 
@@ -172,52 +168,15 @@ def test_rtm_always_aborts(space):
 
 
 # ---------------------------------------------------------------- engine code on the host vs the oracle
-class SimResult(C.Structure):
-    _fields_ = [("gpr", C.c_uint64 * 16), ("rip", C.c_uint64), ("rflags", C.c_uint64), ("icount", C.c_uint64),
-                ("nbytes", C.c_uint64), ("status", C.c_uint32), ("vector", C.c_uint32), ("error", C.c_uint32),
-                ("ovn", C.c_uint32), ("addr", C.c_uint64), ("dirty", C.c_uint64 * 64), ("xmm", C.c_uint64 * 32),
-                ("mxcsr", C.c_uint32), ("pad", C.c_uint32), ("ymmh", C.c_uint64 * 32), ("win", C.c_uint8 * 512)]
-
-
-def sim_lib():
-    L = C.CDLL(ensure(SIMLANE_SO, os.path.join(HERE, "native")))
-    L.sim_run_full.argtypes = [C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64, C.POINTER(Regs), C.c_uint64,
-                               C.POINTER(SimResult), C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(Regs),
-                               C.c_char_p]
-    return L
-
-
-def sim_lanes(L, sp, st, ln, limit=3000):
-    pfns, blob = sp.phys()
-    arr = (C.c_uint64 * len(pfns))(*pfns)
-    out = []
-    for va, g, flags in ln:
-        r = regs_from_state(st)
-        for k in range(16):
-            r.gpr[k] = g[k]
-        r.rip, r.rflags = va, flags
-        res, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
-        pages = C.create_string_buffer(64 * 4096)
-        L.sim_run_full(arr, blob, len(pfns), C.byref(r), limit, C.byref(res), 1, C.byref(cnt), 0, C.byref(fin), pages)
-        n = min(res.ovn, 64)
-        pg = {int(res.dirty[k]): pages.raw[k * 4096:(k + 1) * 4096] for k in range(n)}
-        out.append(S.lane_view(res.status, res.vector, res.error, res.addr, res.icount, res.nbytes, fin, pg))
-    return out
-
-
-def _diff(a: dict, b: dict):
-    return [k for k in a if a[k] != b[k]]
-
-
 def test_engine_code_matches_oracle(space):
     sp, st, lay, data = space
     ln = S.lanes(1600, 11, st, lay, data)
     want = S.oracle_run(sp, st, ln)
-    got = sim_lanes(sim_lib(), sp, st, ln)
+    got = S.sim_lanes(sp, st, ln)
     names = {v: k for k, v in {**S.KSLOT, **S.USLOT}.items()}
     bad = []
     for i, (w, g) in enumerate(zip(want, got)):
-        d = _diff(g, w)
+        d = S.diff(g, w)
         if d:
             nm = names.get(ln[i][0]) or names.get(ln[i][1][3])
             bad.append((i, nm, d, {k: (g[k], w[k]) for k in d if k not in ("pages", "xmm", "ymmh")}))
@@ -262,7 +221,7 @@ def test_gpu_matches_oracle(space):
             e = ex[i]
             pg = {gpa: eng.read_phys(i, gpa, 4096) for gpa in eng.dirty(i)}
             got = S.lane_view(e.status, e.vector, e.error, e.addr, e.icount, int(nb[i]), regs[i], pg)
-            d = _diff(got, w)
+            d = S.diff(got, w)
             if d:
                 bad.append((i, d, {k: (got[k], w[k]) for k in d if k not in ("pages", "xmm", "ymmh")}))
         assert not bad, f"{len(bad)}/{n} lanes differ; first: {bad[:3]}"

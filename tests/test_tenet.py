@@ -21,20 +21,11 @@ import pytest
 
 from tests import progfuzz
 from tests import tlv_harness as H
+from tests import simlane
 from tests.oracle_lib import Oracle
-from tests.test_mmx import sim_lib as _sim_lib
-from tests.test_sse import SimResult
-from wtf_amd.abi import Regs, regs_from_state
+from wtf_amd.abi import regs_from_state
 
 CAP = 1 << 22
-
-
-def sim_lib():
-    L = _sim_lib()
-    L.sim_set_tenet.argtypes = [C.c_uint64]
-    L.sim_tenet.argtypes = [C.c_char_p, C.c_uint64]
-    L.sim_tenet.restype = C.c_uint64
-    return L
 
 
 def parse(stream: bytes):
@@ -56,7 +47,7 @@ def parse(stream: bytes):
 
 @pytest.mark.parametrize("sse", [False, True])
 def test_engine_stream_equals_oracle_on_random_programs(sse):
-    L = sim_lib()
+    L = simlane.lib()
     n = 120
     sp, st, lanes = progfuzz.build(n, seed=77 if sse else 78, sse=sse)
     xmm = progfuzz.lane_xmm(n, 77)
@@ -65,7 +56,7 @@ def test_engine_stream_equals_oracle_on_random_programs(sse):
     o = Oracle(pfns=pfns, blob=blob)
     o.set_limit(3000)
     base = regs_from_state(st)
-    arr = (C.c_uint64 * len(pfns))(*pfns)
+    img = simlane.image(sp)
     bad, accs = [], 0
     for i, (va, g, flags) in enumerate(lanes):
         r = regs_from_state(st)
@@ -80,9 +71,7 @@ def test_engine_stream_equals_oracle_on_random_programs(sse):
         o.run()
         want = o.tenet()
         L.sim_set_tenet(CAP)
-        out, final = SimResult(), Regs()
-        cnt = C.c_uint64(0)
-        L.sim_run_full(arr, blob, len(pfns), C.byref(r), 3000, C.byref(out), 0, C.byref(cnt), 0, C.byref(final), None)
+        simlane.run(img, r, limit=3000)
         buf = C.create_string_buffer(CAP)
         m = L.sim_tenet(buf, CAP)
         got = buf.raw[:m]

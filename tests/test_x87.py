@@ -8,48 +8,23 @@ GPU runs the same vectors in tests/test_gpu_sse.py. Hand-checked here: #UD /
 #NM / #MF / UNIMPLEMENTED, stores that fault, FNINIT, the FSW that a loaded
 image normalises, and the MMX exponent words.
 """
-import gzip
-import json
-import os
-
 import pytest
 
+from tests import simlane
 from tests.golden.gen_x87_vectors import case_regs, mem_forms, reg_forms, run_oracle
-from tests.oracle_lib import Oracle
-from tests.test_mmx import sim_lib, sim_run
-from tests.test_sse import BUF, layout
+from tests.insn_cases import BUF, layout, oracle_of
+from tests.vector_replay import X87, replay_oracle, replay_sim, run_family
 from wtf_amd.abi import EXIT_FAULT, EXIT_UNIMPLEMENTED
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+DOC = X87.doc
 
 
-def load():
-    with gzip.open(os.path.join(HERE, "golden", "x87_vectors.json.gz"), "rt") as f:
-        return json.load(f)
-
-
-DOC = load()
-
-
-def norm_st(st):
-    return [tuple(x) for x in st]
-
-
-def mismatch(c, got):
-    want = c["out"]
-    for k in ("status", "vector", "fcw", "fsw", "ftw", "fl", "mem"):
-        if got[k] != want[k]:
-            return (k, got[k], want[k])
-    if norm_st(got["st"]) != norm_st(want["st"]):
-        return ("st",)
-    return None
-
-
-def run_sim(L, c, buf_va):
-    sp, regs = layout(bytes.fromhex(c["code"]), buf_va, bytes.fromhex(c["mem"]).ljust(256, b"\0"))
+def run_sim(c, buf_va):
+    """One case through the engine's host build, in run_oracle's form."""
+    sp, regs = layout(bytes.fromhex(c["code"]), buf_va, bytes.fromhex(c["mem"]))
     regs.gpr[6] = buf_va
     case_regs(c, regs)
-    out, r = sim_run(L, sp, regs, win_va=buf_va)
+    out, r, _ = simlane.run(sp, regs, win_va=buf_va)
     st = 0 if out.status == 3 else out.status
     return dict(status=st, vector=out.vector if st == EXIT_FAULT else 0, fcw=r.fpcw, fsw=r.fpsw, ftw=r.fptw,
                 st=[(r.fpst[i], r.fpse[i]) for i in range(8)], fl=r.rflags & 0x8D5, mem=bytes(out.win[:16]).hex())
@@ -57,25 +32,16 @@ def run_sim(L, c, buf_va):
 
 @pytest.mark.parametrize("chunk", range(2))
 def test_oracle_matches_x87_vectors(chunk):
-    buf_va = int(DOC["buf_va"], 16)
-    fails = []
-    for c in DOC["cases"][chunk::2]:
-        bad = mismatch(c, run_oracle(c, buf_va))
-        if bad:
-            fails.append((c["code"],) + bad)
-    assert not fails, f"{len(fails)} mismatches, first: {fails[:5]}"
+    cases = DOC["cases"][chunk::2]
+    fails = run_family(X87, replay_oracle, cases)
+    assert not fails, f"{len(fails)}/{len(cases)} mismatches, first: {fails[:5]}"
 
 
 @pytest.mark.parametrize("chunk", range(2))
 def test_engine_x87_code_matches_vectors(chunk):
-    L = sim_lib()
-    buf_va = int(DOC["buf_va"], 16)
-    fails = []
-    for c in DOC["cases"][chunk::2]:
-        bad = mismatch(c, run_sim(L, c, buf_va))
-        if bad:
-            fails.append((c["code"],) + bad)
-    assert not fails, f"{len(fails)} mismatches, first: {fails[:5]}"
+    cases = DOC["cases"][chunk::2]
+    fails = run_family(X87, replay_sim, cases)
+    assert not fails, f"{len(fails)}/{len(cases)} mismatches, first: {fails[:5]}"
 
 
 def test_x87_vector_file_covers_every_form():
@@ -119,20 +85,17 @@ X87_FAULT_CASES = [
 
 @pytest.mark.parametrize("code,status,vector,kw", X87_FAULT_CASES)
 def test_x87_faults_oracle_and_engine(code, status, vector, kw):
-    L = sim_lib()
     c = x87_case(code, **kw)
-    for got in (run_oracle(c, BUF), run_sim(L, c, BUF)):
+    for got in (run_oracle(c, BUF), run_sim(c, BUF)):
         assert got["status"] == status, (bytes(code).hex(), got["status"], got["vector"])
         if vector is not None:
             assert got["vector"] == vector
 
 
 def test_x87_nm_when_cr0_ts():
-    L = sim_lib()
     sp, regs = layout(bytes([0xD9, 0xE8]), BUF, bytes(256), cr0=0x80050033 | 8)
-    out, _ = sim_run(L, sp, regs)
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    out, _, _ = simlane.run(sp, regs)
+    o = oracle_of(sp)
     o.restore(regs)
     ex = o.step()
     assert (out.status, out.vector) == (EXIT_FAULT, 7) and (ex.status, ex.vector) == (EXIT_FAULT, 7)
@@ -147,11 +110,9 @@ def prog_state(code, st0=ONE):
 
 
 def run_both(code):
-    L = sim_lib()
     sp, regs = prog_state(code)
-    out, fin = sim_run(L, sp, regs, win_va=BUF)
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    out, fin, _ = simlane.run(sp, regs, win_va=BUF)
+    o = oracle_of(sp)
     o.restore(regs)
     for _ in range(64):
         ex = o.step()
@@ -187,12 +148,10 @@ def test_fxrstor_normalises_es():
     img[0:2] = (0x37E).to_bytes(2, "little")
     img[2:4] = (0x0001).to_bytes(2, "little")
     img[24:28] = (0x1F80).to_bytes(4, "little")
-    L = sim_lib()
     sp, regs = layout(bytes([0x0F, 0xAE, 0x0E, 0xDF, 0xE0]), BUF, bytes(img[:256]))
     regs.gpr[6] = BUF
-    out, fin = sim_run(L, sp, regs)
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    out, fin, _ = simlane.run(sp, regs)
+    o = oracle_of(sp)
     o.restore(regs)
     o.step()
     o.step()
@@ -201,13 +160,11 @@ def test_fxrstor_normalises_es():
 
 
 def _env_prog(code, data):
-    L = sim_lib()
     sp, regs = layout(bytes(code), BUF, bytes(data) + bytes(256 - len(data)))
     regs.gpr[6], regs.gpr[7] = BUF, BUF + 0x80
     regs.fpcw, regs.fptw = 0x37F, 0xFFFF
-    out, fin = sim_run(L, sp, regs, win_va=BUF)
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    out, fin, _ = simlane.run(sp, regs, win_va=BUF)
+    o = oracle_of(sp)
     o.restore(regs)
     for _ in range(16):
         if o.step().status != 0:
@@ -236,8 +193,7 @@ def test_fldenv_frstor_normalise_fcw_and_retag():
 
 def test_x87_store_fault_leaves_the_stack():
     # fstp dword [rsi + 0x2000] (unmapped): #PF (write), TOP and ST0 unchanged
-    L = sim_lib()
     c = x87_case([0xD9, 0x9E, 0x00, 0x20, 0x00, 0x00], fsw=0x3800, ftw=0x3FFF, st=[ONE] + [(0, 0)] * 7)
-    for got in (run_oracle(c, BUF), run_sim(L, c, BUF)):
+    for got in (run_oracle(c, BUF), run_sim(c, BUF)):
         assert (got["status"], got["vector"]) == (EXIT_FAULT, 14)
         assert got["fsw"] == 0x3800 and tuple(got["st"][0]) == ONE

@@ -11,18 +11,15 @@ fields alone when RFBM[0] = 0, and XSAVEC writes MXCSR only with RFBM[1]).
 XRSTOR of each full image (its header's untouched bytes cleared) restores
 the state it came from.
 """
-import ctypes as C
 import json
 import os
 import struct
 
 import pytest
 
-from tests.cpu_bins import SIMLANE_SO, ensure
-from tests.oracle_lib import Oracle
-from tests.test_avx512 import get_zmm, set_zmm
-from tests.test_sse import SimResult
-from wtf_amd.abi import Regs, regs_from_state
+from tests import simlane
+from tests.insn_cases import get_zmm, oracle_of, set_zmm
+from wtf_amd.abi import regs_from_state
 from wtf_amd.tools.snapshot import AddressSpace, user_state
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,24 +51,17 @@ def space(code, buf=None):
 
 
 def run_oracle(sp, regs):
-    pfns, blob = sp.phys()
-    o = Oracle(pfns=pfns, blob=blob)
+    o = oracle_of(sp)
     o.restore(regs)
     ex = o.step()
     return ex, o.regs(), o.read_virt(BUF_VA, SPAN)
 
 
 def run_sim(sp, regs):
-    L = C.CDLL(ensure(SIMLANE_SO, os.path.join(HERE, "native")))
-    L.sim_run_full.argtypes = [C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64, C.POINTER(Regs), C.c_uint64,
-                               C.POINTER(SimResult), C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(Regs),
-                               C.c_char_p]
     pfns, blob = sp.phys()
-    arr = (C.c_uint64 * len(pfns))(*pfns)
-    out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
-    pages = C.create_string_buffer(64 * 4096)
-    L.sim_run_full(arr, blob, len(pfns), C.byref(regs), 1, C.byref(out), 0, C.byref(cnt), 0, C.byref(fin), pages)
-    dirty = {int(out.dirty[k]): pages.raw[k * 4096:(k + 1) * 4096] for k in range(min(out.ovn, 64))}
+    pages = simlane.page_buffer()
+    out, fin, _ = simlane.run(sp, regs, limit=1, pages=pages)
+    dirty = simlane.dirty_pages(out, pages)
     mem = bytearray()
     for off in range(0, SPAN, 4096):
         pa = sp.translate(BUF_VA + off) & ~0xFFF

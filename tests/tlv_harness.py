@@ -4,6 +4,8 @@ from __future__ import annotations
 
 import json
 import os
+import shutil
+import socket
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,3 +56,38 @@ def fuzz(exe: str, target: str, runs: int, lanes: int, seed: int = 1337, limit: 
         cmd += ["--seconds", str(seconds)]
     out = subprocess.run(cmd, check=True, timeout=timeout, capture_output=True, text=True).stdout
     return json.loads([line for line in out.splitlines() if line.startswith("{")][-1])
+
+
+# ---- campaigns of the twin binary that more than one test file runs
+def free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def fuzz_cmd(d, rank, world, port, runs=3072, lanes=512):
+    return [TWIN, "fuzz", "--name", "tlv_server", "--target", d, "--runs", str(runs), "--lanes", str(lanes),
+            "--seed", "1337", "--limit", "100000", "--rank", str(rank), "--world", str(world),
+            "--exchange", f"127.0.0.1:{port}"]
+
+
+def last_json(out):
+    return json.loads([x for x in out.splitlines() if x.startswith("{")][-1])
+
+
+STREAM_KEYS = ("execs", "retired", "coverage", "corpus", "crashes", "unique_crashes", "timeouts", "cr3", "errors",
+        "error_retired")
+
+
+def stream_campaign(base, d, name, runs, lanes, stream, extra=(), limit=100000, max_len=0x1000):
+    shutil.copytree(base, d, ignore=shutil.ignore_patterns("outputs", "crashes", "work", "errors"))
+    env = {**os.environ, "WTF_TWIN_STREAM": "1" if stream else "0"}
+    out = subprocess.run([TWIN, "fuzz", "--name", name, "--target", d, "--runs", str(runs), "--lanes", str(lanes),
+                          "--seed", "1337", "--limit", str(limit), "--max_len", str(max_len), *extra],
+                         check=True, capture_output=True, text=True, timeout=600, env=env).stdout
+    st = last_json(out)
+    files = tuple(sorted(os.listdir(os.path.join(d, sub))) if os.path.isdir(os.path.join(d, sub)) else []
+                  for sub in ("outputs", "crashes", "errors"))
+    return {k: st[k] for k in STREAM_KEYS}, files
