@@ -19,14 +19,29 @@ def case_id(c):
 
 
 class Workload:
-    def __init__(self, case):
+    """private_code: the lanes with i % 4 in {1, 3} get one byte of each page
+    of their program written by the host before they run, with the value it
+    has: the same programs, run from the lane's own copies of their pages
+    (k_run's slow_step) next to lanes of the same program that run the pool's
+    (lanes 4j .. 4j + 3 share a program). n: the lane count (the first n lanes
+    of the N-lane workload)."""
+
+    def __init__(self, case, n=N, private_code=False):
         seed, sse, fp, evex = case
         self.case = case
         self.evex = evex
+        self.n = n
         self.sp, self.st, self.lanes, self.progs = progfuzz.build_shared_info(N, N_PROGRAMS, seed, sse=sse, fp=fp,
                                                                               evex=evex)
-        self.kw = progfuzz.lane_state(N, seed, sse, evex)
-        self.want = progfuzz.oracle_run(self.sp, self.st, self.lanes, limit=LIMIT, more=MORE, **self.kw)
+        self.lanes = self.lanes[:n]
+        self.kw = {k: v[:n] for k, v in progfuzz.lane_state(N, seed, sse, evex).items()}
+        self.writes = None
+        if private_code:
+            self.writes = [[(va + off, bytes(self.sp.pages[self.sp.translate(va + off) >> 12][:1]))
+                            for off in range(0, progfuzz.SLOT, 0x1000)] if i % 4 in (1, 3) else []
+                           for i, (va, _, _) in enumerate(self.lanes)]
+        self.want = progfuzz.oracle_run(self.sp, self.st, self.lanes, limit=LIMIT, more=MORE, writes=self.writes,
+                                        **self.kw)
         self._bp = None
 
     def breakpoints(self):
@@ -49,7 +64,8 @@ class Workload:
         """The oracle's run over the breakpoints: "stops" per lane, same final state."""
         if self._bp is None:
             self._bp = progfuzz.oracle_run(self.sp, self.st, self.lanes, limit=LIMIT, more=MORE,
-                                           breakpoints=self.breakpoints(), follow_bps=True, **self.kw)
+                                           breakpoints=self.breakpoints(), follow_bps=True, writes=self.writes,
+                                           **self.kw)
         return self._bp
 
 
@@ -65,7 +81,7 @@ def make_engine(w, breakpoints=(), code_pages=False):
     eng = Engine(0)
     pfns, blob = w.sp.phys()
     eng.load_pool(pfns, blob)
-    eng.alloc_lanes(N, overlay_pages=16, cov_entries=4096)
+    eng.alloc_lanes(w.n, overlay_pages=16, cov_entries=4096)
     eng.set_initial_state(regs_from_state(w.st))
     eng.set_limit(LIMIT)
     if breakpoints:
@@ -78,7 +94,7 @@ def make_engine(w, breakpoints=(), code_pages=False):
 
 def load_lanes(eng, w):
     eng.restore()
-    regs = eng.read_regs(0, N)
+    regs = eng.read_regs(0, w.n)
     for i, (va, g, flags) in enumerate(w.lanes):
         r = regs[i]
         for k in range(16):
@@ -86,6 +102,8 @@ def load_lanes(eng, w):
         r.rip, r.rflags = va, flags
         progfuzz.set_lane_state(r, i, **w.kw)
     eng.write_regs(regs)
+    if w.writes:
+        eng.apply_writes([(i, va, data) for i, ws in enumerate(w.writes) for va, data in ws])
 
 
 class Totals:
@@ -109,7 +127,7 @@ def run_sliced(eng, steps, tot=None, use_async=False):
     # a wave of 64 lanes at 2000 instructions each cannot take more wave-steps
     for _ in range(64 * (LIMIT + 1) // steps + 2):
         if use_async:
-            eng.run_async(0, N, steps)
+            eng.run_async(0, eng.nlanes, steps)
             tot.add(eng.run_wait())
         else:
             tot.add(eng.run(max_steps=steps))
@@ -121,7 +139,7 @@ def run_sliced(eng, steps, tot=None, use_async=False):
 def differences(eng, w, want, cov=True):
     """Per-lane bit-exact comparison with the oracle's results."""
     ex = eng.exits()
-    out = eng.read_regs(0, N)
+    out = eng.read_regs(0, w.n)
     covs, ovf = eng.coverage()
     assert not ovf
     nb = eng.nbytes()
@@ -163,7 +181,7 @@ def differences(eng, w, want, cov=True):
 
 def check(eng, w, want, shape, retired=None, cov=True):
     bad = differences(eng, w, want, cov=cov)
-    assert not bad, (f"{case_id(w.case)} / {shape}: {len(bad)}/{N} lanes differ; "
+    assert not bad, (f"{case_id(w.case)} / {shape}: {len(bad)}/{w.n} lanes differ; "
                      f"first (lane, program, what, got, expected): {bad[:3]}")
     if retired is not None:
         assert retired == sum(x["icount"] for x in want), shape

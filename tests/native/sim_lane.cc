@@ -13,8 +13,12 @@ using namespace wtfgpu_dev;
 static std::vector<uint8_t> g_tn_store;
 static uint64_t g_tn_pos, g_tn_cpos, g_tn_ipos, g_tn_last;
 static uint32_t g_tn_mute;
+// Host writes of the next sim_run_full, applied to the lane before it runs
+// (sim_set_writes): records of u64 va, u64 len, then the bytes.
+static std::vector<uint8_t> g_pre;
 
 extern "C" {
+void sim_set_writes(const uint8_t *recs, uint64_t n) { g_pre.assign(recs, recs + n); }
 void sim_set_tenet(uint64_t cap) { g_tn_store.assign(cap, 0); }
 uint64_t sim_tenet(uint8_t *out, uint64_t cap) {
   const uint64_t n = g_tn_pos < g_tn_store.size() ? g_tn_pos : g_tn_store.size();
@@ -102,6 +106,28 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
   L.status = WTFGPU_RUNNING;
   L.simd = simd_bits(r0->cr0, r0->cr4, r0->xcr0);
   tlb_flush(L);
+  // the host's writes before the run (engine_run.h host_write: as supervisor,
+  // CR0.WP clear, through copy-on-write); a write that does not translate ends here
+  for (size_t at = 0; at + 16 <= g_pre.size();) {
+    uint64_t va, n;
+    memcpy(&va, &g_pre[at], 8);
+    memcpy(&n, &g_pre[at + 8], 8);
+    at += 16;
+    const uint32_t cpl0 = L.cpl;
+    const uint64_t cr00 = L.cr0;
+    L.cpl = 0;
+    L.cr0 &= ~(1ull << 16);
+    for (uint64_t i = 0; i < n && L.status == WTFGPU_RUNNING; i++) {
+      uint64_t td;
+      if (service_miss(P, L, va + i, ACC_W) && tlb_get(L, (va + i) >> 12, td))
+        ((uint8_t *)(uintptr_t)(td & ~0xfffull))[(va + i) & 0xfff] = g_pre[at + i];
+    }
+    L.cpl = cpl0;
+    L.cr0 = cr00;
+    tlb_flush(L);
+    at += n;
+  }
+  g_pre.clear();
   g_tn = TenetDev{};
   if (!g_tn_store.empty()) {
     g_tn_pos = g_tn_cpos = g_tn_ipos = 0;

@@ -142,6 +142,9 @@ class Oracle:
         self.L.orc_read_phys(self.m, gpa, b, n)
         return b.raw
 
+    def write_phys(self, gpa, data: bytes):
+        self.L.orc_write_phys(self.m, gpa, data, len(data))
+
     def inject_fault(self, vector, error, addr) -> bool:
         return bool(self.L.orc_inject_fault(self.m, vector, error, addr))
 

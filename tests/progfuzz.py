@@ -604,12 +604,14 @@ def get_zmm(r):
 
 
 def oracle_run(sp: AddressSpace, st: dict, lanes, limit=20000, breakpoints=(), xmm=None, ymmh=None, mxcsr=None,
-               more=(), follow_bps=False, zmm=None, k=None):
+               more=(), follow_bps=False, zmm=None, k=None, writes=None):
     """Runs every lane on the CPU oracle; returns per-lane result dicts. more:
     further (va, length) ranges to read back ("more"). follow_bps: resume over
     every breakpoint hit (run(skip_bp=True)) until another exit, recording the
     hits as "stops": [(rip, icount, gprs)]. zmm / k: the per-lane AVX-512
-    state (lane_zmm, lane_k); "zmm" (256 u64) and "k" (8) come back per lane."""
+    state (lane_zmm, lane_k); "zmm" (256 u64) and "k" (8) come back per lane.
+    writes: per lane, the (va, bytes) the host writes into the lane's memory
+    before it runs (VirtWrite: present bits only, the frames become dirty)."""
     from tests.oracle_lib import Oracle
 
     pfns, blob = sp.phys()
@@ -627,6 +629,8 @@ def oracle_run(sp: AddressSpace, st: dict, lanes, limit=20000, breakpoints=(), x
         r.rflags = flags
         o.restore(base)
         o.set_regs(r)
+        for va_, data in (writes[i] if writes else ()):
+            o.write_virt(va_, data)
         ex = o.run()
         stops = []
         while follow_bps and ex.status == 1:  # EXIT_BREAKPOINT

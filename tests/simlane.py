@@ -3,6 +3,7 @@ lane of k_run's decode / exec / retry loop) built for the host."""
 import ctypes as C
 import functools
 import os
+import struct
 
 from tests.cpu_bins import SIMLANE_SO, ensure
 from wtf_amd.abi import Regs
@@ -31,6 +32,7 @@ def lib():
             ("sim_digest", [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)], C.c_int),
             ("sim_translate", space + [C.c_uint64, C.c_uint64, U64P], C.c_int),
             ("sim_set_tenet", [C.c_uint64], None),
+            ("sim_set_writes", [C.c_char_p, C.c_uint64], None),
             ("sim_tenet", [C.c_char_p, C.c_uint64], C.c_uint64),
             ("sim_result_size", [], C.c_uint64)):
         f = getattr(L, name)
@@ -45,13 +47,17 @@ def image(sp):
     return (C.c_uint64 * len(pfns))(*pfns), blob, len(pfns)
 
 
-def run(sp, regs, limit=0, fast=False, win_va=0, pages=None):
+def run(sp, regs, limit=0, fast=False, win_va=0, pages=None, writes=()):
     """One lane from `regs` until it stops: (SimResult, the merged final Regs,
     the instructions the fast loop's forms retired). sp: an AddressSpace, or
     its image() where many lanes share one. fast=True tries the fast loop's
     form of each instruction first (k_run's order); `win_va` selects the 512
-    bytes returned in `win`; `pages` (a 64-page buffer) receives the dirty pages."""
+    bytes returned in `win`; `pages` (a 64-page buffer) receives the dirty pages;
+    `writes`: (va, bytes) the host writes into the lane's memory before it runs."""
     arr, blob, n = sp if isinstance(sp, tuple) else image(sp)
+    if writes:
+        recs = b"".join(struct.pack("<QQ", va, len(data)) + bytes(data) for va, data in writes)
+        lib().sim_set_writes(recs, len(recs))
     out, fin, cnt = SimResult(), Regs(), C.c_uint64(0)
     lib().sim_run_full(arr, blob, n, C.byref(regs), limit, C.byref(out), 1 if fast else 0, C.byref(cnt), win_va,
                        C.byref(fin), pages)

@@ -75,6 +75,7 @@ struct wtfgpu_ctx {
   u8 *d_pool = nullptr;
   u32 *d_pfnmap = nullptr;
   u32 *d_ptbits = nullptr;
+  u64 *d_codeowner = nullptr;
   u64 npool = 0;
   // lanes
   u64 *d_gpr = nullptr, *d_rip = nullptr, *d_rflags = nullptr, *d_fsb = nullptr, *d_gsb = nullptr,
@@ -621,6 +622,7 @@ int wtfgpu_destroy(wtfgpu_ctx *c) {
   dfree(c->d_pool);
   dfree(c->d_pfnmap);
   dfree(c->d_ptbits);
+  dfree(c->d_codeowner);
   dfree(c->d_bp);
   dfree(c->d_actkeys);
   dfree(c->d_act);
@@ -646,6 +648,7 @@ int wtfgpu_load_pool(wtfgpu_ctx *c, const uint64_t *gpfns, const uint8_t *pages,
   dfree(c->d_pool);
   dfree(c->d_pfnmap);
   dfree(c->d_ptbits);
+  dfree(c->d_codeowner);
   u64 maxpfn = 0;
   for (u64 i = 0; i < npages; i++) maxpfn = std::max<u64>(maxpfn, gpfns[i]);
   const u64 maplen = npages ? maxpfn + 1 : 1;
@@ -660,12 +663,14 @@ int wtfgpu_load_pool(wtfgpu_ctx *c, const uint64_t *gpfns, const uint8_t *pages,
   }
   if (dalloc(&c->d_pfnmap, maplen)) return WTFGPU_ERR_OOM;
   if (dalloc(&c->d_ptbits, (maplen + 31) / 32)) return WTFGPU_ERR_OOM;
+  if (dalloc(&c->d_codeowner, npages + 1)) return WTFGPU_ERR_OOM;
   HIPCHK(hipMemsetAsync(c->d_pool, 0, WTFGPU_PAGE_SIZE, c->q->stream));
   if (npages)
     HIPCHK(hipMemcpyAsync(c->d_pool + WTFGPU_PAGE_SIZE, pages, npages * WTFGPU_PAGE_SIZE, hipMemcpyHostToDevice,
                           c->q->stream));
   HIPCHK(hipMemcpyAsync(c->d_pfnmap, map.data(), maplen * 4, hipMemcpyHostToDevice, c->q->stream));
   HIPCHK(hipMemsetAsync(c->d_ptbits, 0, (maplen + 31) / 32 * 4, c->q->stream));
+  HIPCHK(hipMemsetAsync(c->d_codeowner, 0, (npages + 1) * 8, c->q->stream));
   HIPCHK(hipStreamSynchronize(c->q->stream));
 
   c->npool = npages;
@@ -676,6 +681,7 @@ int wtfgpu_load_pool(wtfgpu_ctx *c, const uint64_t *gpfns, const uint8_t *pages,
   c->P.pfn_map_len = maplen;
   c->P.npool = npages;
   c->P.ptbits = c->d_ptbits;
+  c->P.code_owner = c->d_codeowner;
   if (c->d_tlbok) HIPCHK(hipMemsetAsync(c->d_tlbok, 0, (u64)c->P.nlanes * 4, c->q->stream));  // old page pointers
   if (guc_clear(c)) return WTFGPU_ERR_HIP;
   HIPCHK(hipStreamSynchronize(c->q->stream));

@@ -73,6 +73,7 @@ struct Dev {
   u64 pfn_map_len;
   u64 npool;             // pages in the pool after the zero page
   const u32 *ptbits;     // bitmap over gpfn: page-table pages of the snapshot
+  u64 *code_owner;       // per pool page: vpn + 1 of the address its uop-cache entries belong to (0: none yet)
   // lanes, SoA
   u32 nlanes;
   u32 K;                 // copy-on-write pages per lane

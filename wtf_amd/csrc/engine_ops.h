@@ -269,6 +269,14 @@ __device__ __forceinline__ u32 zsize(u32 z, u32 osz, u32 p66, bool m32) {
   }
 }
 
+// A field that ends at `end`: 1 while the bytes it asks for are not there (the
+// fetch of the next page faults before the length is judged: fetch faults come
+// before decode faults, U52), 2 when they are and it runs past 15, else 0.
+__device__ __forceinline__ int ib_need(const IBytes &b, u32 end) {
+  if (end > b.avail && b.avail < 15) return 1;
+  return end > 15 ? 2 : 0;
+}
+
 // Decode (uniform). 0 ok, 1 needs bytes beyond avail, 2 longer than 15 (#GP).
 // m32: 32-bit code (compatibility mode, U29): no REX, 32-bit operand and
 // address size, 32-bit stack slots and branch targets, disp32 absolute.
@@ -313,8 +321,7 @@ __device__ __forceinline__ int decode(const IBytes &b, UOp &u, bool m32 = false)
   if ((c == 0xc4 || c == 0xc5) && (!m32 || (ib_at(b, pos) & 0xc0) == 0xc0)) {
     const u32 bad = (p66 || u.rep || rex) ? 1u : 0u;  // a legacy 66 / f2 / f3 / REX before VEX: #UD
     const u32 nb = c == 0xc4 ? 2 : 1;
-    if (pos + nb + 1 > 15) return 2;
-    if (pos + nb + 1 > b.avail) return 1;
+    if (const int r = ib_need(b, pos + nb + 1)) return r;
     const u32 b1 = ib_at(b, pos), b2 = c == 0xc4 ? ib_at(b, pos + 1) : b1;
     pos += nb;
     const u32 vr = ((b1 >> 7) & 1) ^ 1;
@@ -343,8 +350,7 @@ __device__ __forceinline__ int decode(const IBytes &b, UOp &u, bool m32 = false)
   // (engine_avx512.h). Its fields become the REX bits and `vex` with EVX set.
   EForm ef{EZ_NONE, 0, 0, false, false, false, false};
   if (c == 0x62 && !m32 && !vex) {  // (after VEX, c is its opcode byte: 62 is vpunpckldq)
-    if (pos + 4 > 15) return 2;
-    if (pos + 4 > b.avail) return 1;
+    if (const int r = ib_need(b, pos + 4)) return r;
     const u32 p0 = ib_at(b, pos), p1 = ib_at(b, pos + 1), p2 = ib_at(b, pos + 2);
     pos += 3;
     c = ib_at(b, pos++);
@@ -481,16 +487,14 @@ __device__ __forceinline__ int decode(const IBytes &b, UOp &u, bool m32 = false)
           u.scale = sib >> 6;
         }
         if (base == 5 && mod == 0) {
-          if (pos + 4 > 15) return 2;
-          if (pos + 4 > b.avail) return 1;
+          if (const int r = ib_need(b, pos + 4)) return r;
           u.disp = sext(ib_get(b, pos, 4), 4);
           pos += 4;
         } else {
           u.base = (i32)(base | (rexb << 3));
         }
       } else if (rm == 5 && mod == 0) {
-        if (pos + 4 > 15) return 2;
-        if (pos + 4 > b.avail) return 1;
+        if (const int r = ib_need(b, pos + 4)) return r;
         u.riprel = m32 ? 0 : 1;  // 32-bit code: disp32 absolute
         u.disp = sext(ib_get(b, pos, 4), 4);
         pos += 4;
@@ -498,14 +502,12 @@ __device__ __forceinline__ int decode(const IBytes &b, UOp &u, bool m32 = false)
         u.base = (i32)(rm | (rexb << 3));
       }
       if (mod == 1) {
-        if (pos + 1 > 15) return 2;
-        if (pos + 1 > b.avail) return 1;
+        if (const int r = ib_need(b, pos + 1)) return r;
         u.disp = sext(ib_get(b, pos, 1), 1);
         if (vex & EVX) u.disp *= (i64)evex_disp8_n(ef, 16u << evex_ll(vex), (vex >> 22) & 1);  // disp8 * N
         pos += 1;
       } else if (mod == 2) {
-        if (pos + 4 > 15) return 2;
-        if (pos + 4 > b.avail) return 1;
+        if (const int r = ib_need(b, pos + 4)) return r;
         u.disp = sext(ib_get(b, pos, 4), 4);
         pos += 4;
       }
@@ -677,8 +679,7 @@ __device__ __forceinline__ int decode(const IBytes &b, UOp &u, bool m32 = false)
     default: n = 0;
   }
   if (m32 && !map2 && (c == 0x9a || c == 0xea)) n = osz + 2;  // ptr16:32 / ptr16:16
-  if (pos + n > 15) return 2;
-  if (pos + n > b.avail) return 1;
+  if (const int r = ib_need(b, pos + n)) return r;
   const u64 raw = ib_get(b, pos, n);
   // the immediates x86 sign-extends: Ib/Iz of alu/test/push/imul, branch displacements, c7 Iz
   const bool sx = n && (u.op == O_ALU || u.op == O_TEST || u.op == O_PUSH || u.op == O_IMUL || u.op == O_JCC ||

@@ -628,6 +628,33 @@ __device__ __forceinline__ const UOp *uc_uop(const Dev &P, UCUop *uu, u64 key, u
   return &us->u;
 }
 
+// The uop cache (LDS entries, warm images, the shared cache) is keyed by the
+// pool page, and an entry's UC_BP / UC_COVERED flags and logged mask are those
+// of the rip that filled it. A pool page therefore belongs to one virtual page:
+// the first that runs code from it (code_owner, claimed here). A lane that
+// runs the same page at another address gets CPTR_ALIAS in its code pointer,
+// which puts the pointer outside the pool as EFER_M32 does: uncached, every
+// instruction through slow_step, which looks everything up by the lane's rip.
+constexpr u64 CPTR_ALIAS = 1ull << 62;
+__device__ __forceinline__ bool code_page_pooled(const Dev &P, u64 td, u64 &idx) {
+  const u64 o = (td & ~0xfffull) - (u64)(uintptr_t)P.pool;
+  idx = o >> 12;
+  return !(td & T_PRIV) && P.code_owner && o < (P.npool + 1) * WTFGPU_PAGE_SIZE;
+}
+// the fast loop's question (a load, no claim): the page is this address's own
+__device__ __forceinline__ bool code_owner_is(const Dev &P, u64 td, u64 vpn) {
+  u64 idx;
+  // (an atomic load: a claim another wave made is seen, not a cached 0; a stale 0 would only decline)
+  return !code_page_pooled(P, td, idx) ||
+         __hip_atomic_load(&P.code_owner[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == vpn + 1;
+}
+__device__ __forceinline__ u64 code_alias_bit(const Dev &P, u64 td, u64 vpn) {
+  u64 idx;
+  if (!code_page_pooled(P, td, idx)) return 0;
+  const unsigned long long prev = atomicCAS((unsigned long long *)&P.code_owner[idx], 0ull, vpn + 1);
+  return prev == 0 || prev == vpn + 1 ? 0 : CPTR_ALIAS;
+}
+
 // Instruction-page translation for lanes whose code-page cache missed.
 __device__ __noinline__ void code_xlate(const Dev &P, Lane &L, u64 rip) {
   u64 td;
@@ -640,7 +667,7 @@ __device__ __noinline__ void code_xlate(const Dev &P, Lane &L, u64 rip) {
   }
   if (td) {
     L.cvpn = vpn;
-    L.cptr = (td & ~0xfffull) | (L.efer & EFER_M32);  // 32-bit code: outside the pool (U29)
+    L.cptr = (td & ~0xfffull) | (L.efer & EFER_M32) | code_alias_bit(P, td, vpn);  // 32-bit code: outside the pool (U29)
   }
 }
 
@@ -966,7 +993,7 @@ __device__ __noinline__ bool bp_apply(const Dev &P, Lane &L, u64 grip, const wtf
 __device__ __noinline__ void slow_step(const Dev &P, Lane &L, u64 grip, u64 lptr, bool ing, bool &skip) {
   const u32 off = (u32)(grip & 0xfff);
   const bool m32 = (lptr & EFER_M32) != 0;  // the group's lanes run 32-bit code (U29)
-  lptr &= ~EFER_M32;
+  lptr &= ~(EFER_M32 | CPTR_ALIAS);
   IBytes ib;
   ib.avail = 4096 - off < 16 ? 4096 - off : 16;
   fetch_bytes(lptr, off, ib.avail, ib.lo, ib.hi);
@@ -1239,7 +1266,8 @@ __global__ __launch_bounds__(256, 2) void k_run(Dev P, u32 first, u32 count, u64
             tlb_put(L, grip >> 12, td);
             ok = true;
           }
-          if (ok) {
+          // (a pool page this address does not own yet, or shares: code_xlate claims it or marks the alias)
+          if (ok && code_owner_is(P, td, grip >> 12)) {
             L.cvpn = grip >> 12;
             L.cptr = (td & ~0xfffull) | (L.efer & EFER_M32);  // 32-bit code: to slow_step (U29)
           }
