@@ -57,6 +57,7 @@ extern "C" {
 #define WTFGPU_ERR_HIP (-4)
 #define WTFGPU_ERR_STATE (-5)
 #define WTFGPU_ERR_TRANSLATE (-6)
+#define WTFGPU_ERR_FULL (-7) /* wtfgpu_corpus_add: no entry or no bytes left */
 
 /* Per-lane status / exit reasons. A lane with status RUNNING is runnable. */
 enum wtfgpu_status {
@@ -331,11 +332,53 @@ int wtfgpu_restore_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n);
 /* Feeds of a lane list, each in a fixed per-lane region (running lanes keep
  * theirs): lane lanes[i] gets bytes[offsets[i] .. offsets[i+1]); has_feed[i]
  * == 0, or a feed larger than the region, sends that lane's FEED hits to the
- * host handler. Asynchronous on the current queue: `bytes` (pinned memory,
- * wtfgpu_host_alloc, for a DMA) must stay unchanged until the queue's next
- * synchronising call (wtfgpu_run_wait, or any call that returns data). */
+ * host handler. Asynchronous on the current queue. Lifetime of `bytes`
+ * (pinned memory, wtfgpu_host_alloc, for a DMA): the DMA reads them after the
+ * call has returned, and no later wtfgpu_set_feed_lanes or other asynchronous
+ * call waits for it, so they must stay unchanged until a call that waits for
+ * this queue has returned (wtfgpu_run_wait, or any call that returns data).
+ * `lanes`, `offsets` and `has_feed` are copied before the call returns. */
 int wtfgpu_set_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, const uint64_t *offsets,
                           const uint8_t *has_feed, const uint8_t *bytes, uint64_t nbytes);
+/* A lane's feed region (wtfgpu_set_feed_lanes, wtfgpu_mutate_feed_lanes): a
+ * testcase chunk, its u32 size included, is at most this long. */
+#define WTFGPU_FEED_STRIDE 16384u
+
+/* Device corpus and mutator (`wtfgpu fuzz --device-mutate`): testcases are made
+ * on the device from a device-resident copy of the corpus, straight into the
+ * lanes' feed regions. The generator is csrc/engine_mutate.h, which documents
+ * the stream; it is not the reference's.
+ *
+ * wtfgpu_corpus_alloc: an append-only arena of at most max_entries entries and
+ * max_bytes bytes, and its offset table (the device-side stand-in for the
+ * server's Corpus_, server.h:629-714, as far as the mutator reads it);
+ * (0, 0) drops it. Waits for the device.
+ * wtfgpu_corpus_add: appends one entry (len 0 allowed) and gives its index;
+ * complete when it returns. No kernel in flight reads what it writes: a
+ * mutation reads only entries below the ncorpus it was ordered with.
+ * WTFGPU_ERR_FULL when the entries or the bytes are used up; the arena is
+ * unchanged then and later, smaller entries may still fit. */
+int wtfgpu_corpus_alloc(wtfgpu_ctx *ctx, uint64_t max_entries, uint64_t max_bytes);
+int wtfgpu_corpus_add(wtfgpu_ctx *ctx, const uint8_t *bytes, uint64_t len, uint32_t *index);
+/* Stands in for Mutator_t::GetNewTestcase (mutator.cc:8-54) plus the upload:
+ * lane lanes[i] gets, as its feed (one chunk, as wtfgpu_set_feed defines
+ * chunks), testcase indices[i] of the stream `seed` over the first ncorpus[i]
+ * corpus entries, at most max_len bytes long. A declared insert then runs on
+ * the same list, ordered after it, as in wtfgpu_set_feed_lanes. Asynchronous
+ * on the current queue; unlike wtfgpu_set_feed_lanes it reads no caller's
+ * buffer after it returns. WTFGPU_ERR_INVALID, before anything is queued, for
+ * an ncorpus[i] of 0 or above the entries added, a max_len above
+ * WTFGPU_FEED_STRIDE - 4, a lane outside the context, or no arena. */
+int wtfgpu_mutate_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint64_t seed,
+                             const uint64_t *indices, const uint32_t *ncorpus, uint32_t max_len);
+/* The first feed chunk (the testcase) of each listed lane, gathered on the
+ * device: lens[i] is its size (~0u: the lane has no feed), bytes + i * stride
+ * gets its first min(size, stride) bytes. The chunk stays in place after the
+ * declared insert has consumed the feed, until the lane's next feed. Waits for
+ * the current queue (the server keeps the testcase it sent instead,
+ * server.h:629-714). */
+int wtfgpu_read_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t *lens, uint8_t *bytes,
+                           uint64_t stride);
 /* New-coverage sets of a lane list (as wtfgpu_read_coverage); a call whose
  * cap covers the count also empties those lanes' sets (cap = 0 with an empty
  * result included). */

@@ -76,6 +76,14 @@ class SpillStats(C.Structure):
                                           "pool_empty", "claims")]
 
 
+class Insert(C.Structure):
+    """wtfgpu_insert_t"""
+    _fields_ = [(k, C.c_uint32) for k in ("head_reg", "ptr_reg", "len_reg", "len_arg")]
+
+
+ERR_INVALID, ERR_FULL = -1, -7
+FEED_STRIDE = 16384  # WTFGPU_FEED_STRIDE: a testcase chunk is at most FEED_STRIDE - 4 bytes
+
 SEG_ORDER = ["es", "cs", "ss", "ds", "fs", "gs", "tr", "ldtr"]
 GPR_ORDER = ["rax", "rcx", "rdx", "rbx", "rsp", "rbp", "rsi", "rdi",
              "r8", "r9", "r10", "r11", "r12", "r13", "r14", "r15"]
@@ -177,6 +185,12 @@ def load_hip_library(path: str = LIB_PATH) -> C.CDLL:
         "wtfgpu_lane_get_cr": ([P, U32, U32, C.POINTER(U64)], C.c_int),
         "wtfgpu_lane_set_cr": ([P, U32, U32, U64], C.c_int),
         "wtfgpu_coverage_absorb": ([P, C.POINTER(U64), U64, C.POINTER(U64)], C.c_int),
+        "wtfgpu_set_insert": ([P, C.POINTER(Insert)], C.c_int),
+        "wtfgpu_set_feed_lanes": ([P, C.POINTER(U32), U32, C.POINTER(U64), C.c_char_p, C.c_char_p, U64], C.c_int),
+        "wtfgpu_corpus_alloc": ([P, U64, U64], C.c_int),
+        "wtfgpu_corpus_add": ([P, C.c_char_p, U64, C.POINTER(U32)], C.c_int),
+        "wtfgpu_mutate_feed_lanes": ([P, C.POINTER(U32), U32, U64, C.POINTER(U64), C.POINTER(U32), U32], C.c_int),
+        "wtfgpu_read_feed_lanes": ([P, C.POINTER(U32), U32, C.POINTER(U32), P, U64], C.c_int),
     }
     for name, (args, ret) in sig.items():
         fn = getattr(lib, name)

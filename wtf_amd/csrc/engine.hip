@@ -119,6 +119,12 @@ struct wtfgpu_ctx {
   u64 feed_stride = 0;  // streaming: bytes of feed region per lane (0 = one packed feed)
   bool ins_on = false;  // a declared insert (wtfgpu_set_insert) runs after each feed upload
   wtfgpu_insert_t ins{};
+  // device corpus (wtfgpu_corpus_alloc): an append-only arena and its offset
+  // table (entries + 1 values; the host keeps a copy for the argument checks)
+  u8 *d_corpus = nullptr;
+  u64 *d_corpus_off = nullptr;
+  u64 corpus_max_entries = 0, corpus_max_bytes = 0;
+  std::vector<u64> corpus_off;
   // coverage
   u64 *d_codekeys = nullptr;
   u32 *d_codeslot = nullptr;
@@ -403,6 +409,28 @@ int read_back(wtfgpu_ctx *c, void *dst, const Side &s) {
   return WTFGPU_OK;
 }
 
+// The per-lane feed regions (wtfgpu_set_feed_lanes, wtfgpu_mutate_feed_lanes),
+// made at their first use.
+int feed_regions(wtfgpu_ctx *c) {
+  const u64 N = c->P.nlanes;
+  // first use: buffers change under every queue
+  if (!c->d_feedpos || c->feed_stride == 0) HIPCHK(hipDeviceSynchronize());
+  if (!c->d_feedpos) {
+    if (dalloc(&c->d_feedpos, N) || dalloc(&c->d_feedend, N)) return WTFGPU_ERR_OOM;
+    std::vector<u64> none(N, ~0ull);
+    HIPCHK(hipMemcpy(c->d_feedpos, none.data(), N * 8, hipMemcpyHostToDevice));
+  }
+  if (c->feed_stride == 0) {  // switch to per-lane regions (a packed feed's lanes are finished by now)
+    const u64 stride = WTFGPU_FEED_STRIDE;
+    dfree(c->d_feeddata);
+    c->feed_cap = 0;
+    if (dalloc(&c->d_feeddata, N * stride)) return WTFGPU_ERR_OOM;
+    c->feed_cap = N * stride;
+    c->feed_stride = stride;
+  }
+  return WTFGPU_OK;
+}
+
 constexpr u32 kExtraEntries = 1u << 20;
 
 // The warm images of every queue dropped (rare: setup-time changes). Every
@@ -627,6 +655,8 @@ int wtfgpu_destroy(wtfgpu_ctx *c) {
   dfree(c->d_actkeys);
   dfree(c->d_act);
   dfree(c->d_feeddata);
+  dfree(c->d_corpus);
+  dfree(c->d_corpus_off);
   dfree(c->d_codekeys);
   dfree(c->d_codeslot);
   dfree(c->d_covmap);
@@ -1023,22 +1053,7 @@ int wtfgpu_set_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, cons
   }
   if (n == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  const u64 N = c->P.nlanes;
-  // first use: buffers change under every queue
-  if (!c->d_feedpos || c->feed_stride == 0) HIPCHK(hipDeviceSynchronize());
-  if (!c->d_feedpos) {
-    if (dalloc(&c->d_feedpos, N) || dalloc(&c->d_feedend, N)) return WTFGPU_ERR_OOM;
-    std::vector<u64> none(N, ~0ull);
-    HIPCHK(hipMemcpy(c->d_feedpos, none.data(), N * 8, hipMemcpyHostToDevice));
-  }
-  if (c->feed_stride == 0) {  // switch to per-lane regions (a packed feed's lanes are finished by now)
-    const u64 stride = 16384;
-    dfree(c->d_feeddata);
-    c->feed_cap = 0;
-    if (dalloc(&c->d_feeddata, N * stride)) return WTFGPU_ERR_OOM;
-    c->feed_cap = N * stride;
-    c->feed_stride = stride;
-  }
+  if (int rc = feed_regions(c)) return rc;
   // one staging upload of the lane list, the offsets and the flags (the
   // scatter derives each lane's length, position and end), one of the bytes
   // (straight from the caller's buffer: pinned memory DMAs), then one scatter
@@ -1052,7 +1067,9 @@ int wtfgpu_set_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, cons
                                               S + data.off, c->d_feedpos, c->d_feedend);
   HIPCHK(hipGetLastError());
   // no wait: the queue's later work (its k_run slice) is ordered after the
-  // scatter, and the next call on this queue synchronises first
+  // scatter. Nothing here or in the queue's next call waits for the DMA of
+  // `bytes`: the caller keeps them unchanged until a call of its own waits for
+  // the queue (wtfgpu_run_wait, or any call that returns data).
   c->P.feed_pos = c->d_feedpos;
   c->P.feed_end = c->d_feedend;
   c->P.feed_data = c->d_feeddata;
@@ -1060,6 +1077,101 @@ int wtfgpu_set_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, cons
     k_insert<<<(n + 63) / 64, 64, 0, c->q->stream>>>(c->P, c->ins, (const u32 *)c->q->d_scratch, 0, n);
     HIPCHK(hipGetLastError());
   }
+  return WTFGPU_OK;
+}
+
+// ---- device corpus and mutator (engine_mutate.h)
+
+int wtfgpu_corpus_alloc(wtfgpu_ctx *c, uint64_t max_entries, uint64_t max_bytes) {
+  if (!c || (max_entries == 0) != (max_bytes == 0) || max_entries > 0xffffffffull) return WTFGPU_ERR_INVALID;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());  // a mutation in flight on either queue reads the old arena
+  dfree(c->d_corpus);
+  dfree(c->d_corpus_off);
+  c->corpus_max_entries = c->corpus_max_bytes = 0;
+  c->corpus_off.clear();
+  if (max_entries == 0) return WTFGPU_OK;
+  if (dalloc(&c->d_corpus, max_bytes) || dalloc(&c->d_corpus_off, max_entries + 1)) {
+    dfree(c->d_corpus);
+    dfree(c->d_corpus_off);
+    return WTFGPU_ERR_OOM;
+  }
+  HIPCHK(hipMemset(c->d_corpus_off, 0, 8));
+  c->corpus_max_entries = max_entries;
+  c->corpus_max_bytes = max_bytes;
+  c->corpus_off.assign(1, 0);
+  return WTFGPU_OK;
+}
+
+int wtfgpu_corpus_add(wtfgpu_ctx *c, const uint8_t *bytes, uint64_t len, uint32_t *index) {
+  if (!c || !c->d_corpus || (len && !bytes)) return WTFGPU_ERR_INVALID;
+  const u64 count = c->corpus_off.size() - 1, used = c->corpus_off.back();
+  if (count >= c->corpus_max_entries || len > c->corpus_max_bytes - used) return WTFGPU_ERR_FULL;
+  HIPCHK(hipSetDevice(c->device));
+  // Blocking copies on the null stream (the queues' streams do not wait for
+  // it): complete on return, so a mutation ordered later sees the entry, and
+  // one in flight reads only entries below its own ncorpus, written before.
+  if (len) HIPCHK(hipMemcpy(c->d_corpus + used, bytes, len, hipMemcpyHostToDevice));
+  const u64 end = used + len;
+  HIPCHK(hipMemcpy(c->d_corpus_off + count + 1, &end, 8, hipMemcpyHostToDevice));
+  c->corpus_off.push_back(end);
+  if (index) *index = (u32)count;
+  return WTFGPU_OK;
+}
+
+int wtfgpu_mutate_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint64_t seed, const uint64_t *indices,
+                             const uint32_t *ncorpus, uint32_t max_len) {
+  if (!c || !c->d_gpr || !c->d_corpus || (n && (!lanes || !indices || !ncorpus)) ||
+      max_len > WTFGPU_FEED_STRIDE - 4 || !lane_list_in_range(c, lanes, n))
+    return WTFGPU_ERR_INVALID;
+  {  // every order reads entries that exist: the kernel checks nothing
+    const u64 count = c->corpus_off.size() - 1;
+    u32 bad = 0;
+    for (u32 i = 0; i < n; i++) bad |= (u32)(ncorpus[i] == 0) | (u32)(ncorpus[i] > count);
+    if (bad) return WTFGPU_ERR_INVALID;
+  }
+  if (n == 0) return WTFGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = feed_regions(c)) return rc;
+  // one staging upload of the lane list and the orders; no caller's buffer is
+  // read after the call returns (unlike wtfgpu_set_feed_lanes' `bytes`)
+  Side s[] = {side_in(indices, (u64)n * 8), side_in(ncorpus, (u64)n * 4)};
+  if (int rc = stage_lanes(c, Upload::Ring, lanes, n, s, 2)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_mutate_feeds<<<(n + MUT_WAVES - 1) / MUT_WAVES, 64 * MUT_WAVES, 0, c->q->stream>>>(
+      c->d_feeddata, c->feed_stride, (const u32 *)S, (const u64 *)(S + s[0].off), (const u32 *)(S + s[1].off), n, seed,
+      max_len, c->d_corpus, c->d_corpus_off, c->d_feedpos, c->d_feedend);
+  HIPCHK(hipGetLastError());
+  c->P.feed_pos = c->d_feedpos;
+  c->P.feed_end = c->d_feedend;
+  c->P.feed_data = c->d_feeddata;
+  if (c->ins_on) {  // the declared insert of the listed lanes, ordered after the mutation
+    k_insert<<<(n + 63) / 64, 64, 0, c->q->stream>>>(c->P, c->ins, (const u32 *)S, 0, n);
+    HIPCHK(hipGetLastError());
+  }
+  return WTFGPU_OK;
+}
+
+int wtfgpu_read_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32_t *lens, uint8_t *bytes,
+                           uint64_t stride) {
+  if (!c || !c->d_gpr || (n && (!lanes || !lens)) || (n && stride && !bytes) || !lane_list_in_range(c, lanes, n))
+    return WTFGPU_ERR_INVALID;
+  if (n == 0) return WTFGPU_OK;
+  if (!c->d_feedpos || c->feed_stride == 0) {  // no per-lane regions yet: no lane has a feed in one
+    for (u32 i = 0; i < n; i++) lens[i] = ~0u;
+    return WTFGPU_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  Side s[] = {side_room((u64)n * 4), side_room((u64)n * stride)};
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, s, 2)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_feed_gather<<<n, 128, 0, c->q->stream>>>(c->d_feeddata, c->feed_stride, (const u32 *)S, n, c->d_feedpos,
+                                             (u32 *)(S + s[0].off), S + s[1].off, stride);
+  HIPCHK(hipGetLastError());
+  // gathered on the device, so the copy back is the listed lanes' bytes only; one wait
+  HIPCHK(hipMemcpyAsync(lens, S + s[0].off, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
+  if (stride) return read_back(c, bytes, s[1]);
+  HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }
 

@@ -4,6 +4,7 @@
 // Device half of engine.hip (see engine_run.h); included nowhere else.
 #pragma once
 #include "engine_run.h"
+#include "engine_mutate.h"
 
 namespace {
 
@@ -545,6 +546,55 @@ __global__ void k_feed_scatter(u8 *feed, u64 stride, const u32 *lanes, const u64
   u8 *dst = feed + (u64)lane * stride;
   const u8 *sp = src + o;
   for (u64 k = threadIdx.x; k < len; k += blockDim.x) dst[k] = sp[k];
+}
+
+// The device mutator (wtfgpu_mutate_feed_lanes; engine_mutate.h defines the
+// stream): one wave per testcase, MUT_WAVES testcases a block. Testcase i is
+// (seed, index[i]) over the first ncorpus[i] corpus entries; every decision
+// of its plan depends on those alone, so all 64 lanes compute the same plan
+// and then write the chunk k_feed_scatter would have copied, a little-endian
+// u32 size and the bytes, four bytes a lane a round (the region and the bytes
+// after the size are 4-aligned; the last word is zero-padded, inside the
+// region: size <= max_len <= stride - 4).
+constexpr u32 MUT_WAVES = 4;
+__global__ __launch_bounds__(64 * MUT_WAVES) void k_mutate_feeds(u8 *feed, u64 stride, const u32 *lanes,
+                                                                 const u64 *index, const u32 *ncorpus, u32 n, u64 seed,
+                                                                 u32 max_len, const u8 *arena, const u64 *arena_off,
+                                                                 u64 *feed_pos, u64 *feed_end) {
+  const u32 i = blockIdx.x * MUT_WAVES + threadIdx.x / 64, l = threadIdx.x & 63;
+  if (i >= n) return;
+  const u32 lane = lanes[i];
+  wtfmut::Plan p;
+  wtfmut::make_plan(p, seed, index[i], wtfmut::Corpus{arena, arena_off}, ncorpus[i], max_len);
+  u8 *dst = feed + (u64)lane * stride;
+  if (l == 0) {
+    feed_pos[lane] = (u64)lane * stride;
+    feed_end[lane] = (u64)lane * stride + 4 + p.size;
+    *(u32 *)dst = p.size;
+  }
+  for (u32 j = 4 * l; j < p.size; j += 256) {
+    u32 w = 0;
+    for (u32 k = 0; k < 4; k++)
+      if (j + k < p.size) w |= (u32)wtfmut::plan_byte(p, j + k) << (8 * k);
+    *(u32 *)(dst + 4 + j) = w;
+  }
+}
+
+// wtfgpu_read_feed_lanes: the first chunk of each listed lane's feed region
+// (the testcase, which stays there after k_insert has consumed the feed), cut
+// to `room` bytes, one block a lane. len ~0u: the lane has no feed.
+__global__ void k_feed_gather(const u8 *feed, u64 stride, const u32 *lanes, u32 n, const u64 *feed_pos, u32 *lens,
+                              u8 *out, u64 room) {
+  const u32 i = blockIdx.x;
+  if (i >= n) return;
+  const u32 lane = lanes[i];
+  const bool has = feed_pos[lane] != ~0ull;
+  const u8 *src = feed + (u64)lane * stride;
+  u64 len = has ? (u64)src[0] | ((u64)src[1] << 8) | ((u64)src[2] << 16) | ((u64)src[3] << 24) : 0;
+  if (len > stride - 4) len = stride - 4;
+  if (threadIdx.x == 0) lens[i] = has ? (u32)len : ~0u;
+  if (len > room) len = room;
+  for (u64 k = threadIdx.x; k < len; k += blockDim.x) out[(u64)i * room + k] = src[4 + k];
 }
 
 __global__ void k_cov_commit(Dev P, const u64 *rips, u64 n) {

@@ -17,6 +17,10 @@ class EngineError(RuntimeError):
     pass
 
 
+class DeviceCorpusFull(EngineError):
+    pass
+
+
 def _chk(rc, what):
     if rc != 0:
         raise EngineError(f"{what} failed: {rc}")
@@ -92,6 +96,58 @@ class Engine:
     def restore(self, first=0, count=None):
         count = self.nlanes - first if count is None else count
         _chk(self.L.wtfgpu_restore(self.ctx, first, count), "restore")
+
+    # ---- feeds, the declared insert, the device corpus and mutator
+    def set_insert(self, head_reg, ptr_reg, len_reg, len_arg=0):
+        ins = abi.Insert(head_reg, ptr_reg, len_reg, len_arg)
+        _chk(self.L.wtfgpu_set_insert(self.ctx, C.byref(ins)), "set_insert")
+
+    def set_feed_lanes(self, lanes, testcases):
+        """One chunk per lane (a u32 size, then the bytes), as the streaming
+        refill uploads them. The bytes are kept until the next call."""
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        chunks = [len(t).to_bytes(4, "little") + bytes(t) for t in testcases]
+        off = np.zeros(len(la) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(c) for c in chunks])
+        self._feed_keep = b"".join(chunks)
+        _chk(self.L.wtfgpu_set_feed_lanes(self.ctx, la.ctypes.data_as(C.POINTER(C.c_uint32)), len(la),
+                                          off.ctypes.data_as(C.POINTER(C.c_uint64)), None, self._feed_keep,
+                                          len(self._feed_keep)), "set_feed_lanes")
+
+    def corpus_alloc(self, max_entries, max_bytes):
+        _chk(self.L.wtfgpu_corpus_alloc(self.ctx, max_entries, max_bytes), "corpus_alloc")
+
+    def corpus_add(self, data: bytes) -> int:
+        """Index of the new entry; raises DeviceCorpusFull when it does not fit."""
+        idx = C.c_uint32()
+        rc = self.L.wtfgpu_corpus_add(self.ctx, bytes(data), len(data), C.byref(idx))
+        if rc == abi.ERR_FULL:
+            raise DeviceCorpusFull(f"corpus_add: no room for {len(data)} bytes")
+        _chk(rc, "corpus_add")
+        return idx.value
+
+    def mutate_feed_lanes_rc(self, lanes, seed, indices, ncorpus, max_len) -> int:
+        """wtfgpu_mutate_feed_lanes' return code (asynchronous on the queue)."""
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        ix = np.ascontiguousarray(indices, dtype=np.uint64)
+        nc = np.ascontiguousarray(ncorpus, dtype=np.uint32)
+        assert len(ix) == len(la) and len(nc) == len(la)
+        return self.L.wtfgpu_mutate_feed_lanes(self.ctx, la.ctypes.data_as(C.POINTER(C.c_uint32)), len(la), seed,
+                                               ix.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               nc.ctypes.data_as(C.POINTER(C.c_uint32)), max_len)
+
+    def mutate_feed_lanes(self, lanes, seed, indices, ncorpus, max_len):
+        _chk(self.mutate_feed_lanes_rc(lanes, seed, indices, ncorpus, max_len), "mutate_feed_lanes")
+
+    def read_feed_lanes(self, lanes, stride=abi.FEED_STRIDE - 4):
+        """Each listed lane's testcase (None: the lane has no feed)."""
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        lens = np.zeros(len(la), dtype=np.uint32)
+        out = np.zeros((len(la), stride), dtype=np.uint8)
+        _chk(self.L.wtfgpu_read_feed_lanes(self.ctx, la.ctypes.data_as(C.POINTER(C.c_uint32)), len(la),
+                                           lens.ctypes.data_as(C.POINTER(C.c_uint32)), out.ctypes.data_as(C.c_void_p),
+                                           stride), "read_feed_lanes")
+        return [None if n == 0xffffffff else out[i, :min(int(n), stride)].tobytes() for i, n in enumerate(lens)]
 
     # ---- registers
     def read_gprs(self, first=0, count=None) -> np.ndarray:

@@ -277,6 +277,22 @@ bool GpuBackend_t::DeclareInsert(const InsertAction_t &Action) {
   return true;
 }
 
+// --device-mutate: the device corpus and the stream's parameters. Needs the
+// declared insert on the device: nothing else puts an ordered testcase into
+// the guest.
+bool GpuBackend_t::SetDeviceMutate(uint64_t Seed, uint32_t MaxLen, uint64_t MaxEntries, uint64_t MaxBytes) {
+  if (!insert_action_ || MaxLen + 4 > kFeedRegion) return false;
+  if (wtfgpu_corpus_alloc(ctx_, MaxEntries, MaxBytes) != WTFGPU_OK) return false;
+  mut_on_ = true;
+  mut_seed_ = Seed;
+  mut_max_len_ = MaxLen;
+  return true;
+}
+
+bool GpuBackend_t::DeviceCorpusAdd(const uint8_t *P, size_t N) {
+  return mut_on_ && wtfgpu_corpus_add(ctx_, P, N, nullptr) == WTFGPU_OK;
+}
+
 // The testcase as the feed's one chunk (u32 size, bytes); the device applies
 // the declared insert to it before the lane runs.
 bool GpuBackend_t::SetInsert(const uint8_t *Data, const uint64_t Size) {
@@ -1612,6 +1628,7 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
     busy_.assign(nlanes_, 0);
     tag_.assign(nlanes_, 0);
     tc_bytes_.assign(nlanes_, 0);
+    ordered_.assign(nlanes_, 0);
     lres_.assign(nlanes_, LaneResult{});
     plain_.assign(nlanes_, 0);
     const uint32_t n = parts_n();
@@ -1682,6 +1699,14 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
         tag_[l] = In[i].tag;
         tc_bytes_[l] = In[i].size;
         const StreamTestcase_t &T = In[i];
+        ordered_[l] = T.ordered;
+        if (T.ordered) {  // made on the device below: no bytes, no InsertTestcase
+          pf_[l] = f;
+          flen_[i] = 0;
+          fhas_[i] = 0;
+          if (Slots) Slots->ResetLane(l);
+          continue;
+        }
         bool prepared = true;
         switch (T.prep) {
           case PreparedInsert_t::Call: prepared = false; break;
@@ -1757,7 +1782,20 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
         pre_.swap(tmp_lanes_);
       }
     }
-    if (feeds) {
+    // --device-mutate: the ordered lanes, ascending as the fresh lanes are
+    mut_lanes_.clear();
+    mut_idx_.clear();
+    mut_nc_.clear();
+    if (mut_on_)
+      for (size_t i = 0; i < n; i++)
+        if (In[i].ordered) {
+          mut_lanes_.push_back(fresh[i]);
+          mut_idx_.push_back(In[i].index);
+          mut_nc_.push_back(In[i].ncorpus);
+        }
+    // (lanes refilled with bytes in the same step keep the upload path; an
+    // ordered lane has no feed there, and gets its own right after)
+    if (feeds && mut_lanes_.size() < n) {
       const auto tf = Clock::now();
       // the chunks' first offsets, then each chunk's lanes packed into the
       // part's pinned buffer on all host threads: one DMA
@@ -1800,6 +1838,13 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
       if (wtfgpu_set_feed_lanes(ctx_, fresh.data(), (uint32_t)n, foff_.data(), fhas_.data(), P.pin, total))
         return false;
       stats_.up_feed_ms += ms_since(tf);
+    }
+    if (!mut_lanes_.empty()) {
+      const auto tmu = Clock::now();
+      if (wtfgpu_mutate_feed_lanes(ctx_, mut_lanes_.data(), (uint32_t)mut_lanes_.size(), mut_seed_, mut_idx_.data(),
+                                   mut_nc_.data(), mut_max_len_) != WTFGPU_OK)
+        return false;
+      stats_.mutate_dev_ms += ms_since(tmu);
     }
     // lanes InsertTestcase stopped never run: marked STOPPED on the device, so
     // the next classification gives them their result
@@ -2079,6 +2124,25 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
   target_restore(Target, finished, Slots);
   stats_.target_restore_ms += ms_since(tr);
   const auto tout = Clock::now();
+  // --device-mutate: the ordered testcases whose result is not the common
+  // counted one, read back in one call before their lanes are refilled
+  P.rb_lanes.clear();
+  if (mut_on_) {
+    for (uint32_t l : finished)
+      if (ordered_[l] && !plain_[l]) P.rb_lanes.push_back(l);
+    if (!P.rb_lanes.empty()) {
+      const size_t m = P.rb_lanes.size();
+      const uint64_t stride = std::max<uint32_t>(mut_max_len_, 1);
+      P.rb_lens.resize(m);
+      if (P.rb_bytes.size() < m * stride) P.rb_bytes.resize(m * stride);
+      if (wtfgpu_read_feed_lanes(ctx_, P.rb_lanes.data(), (uint32_t)m, P.rb_lens.data(), P.rb_bytes.data(), stride) !=
+          WTFGPU_OK)
+        return false;
+      for (size_t k = 0; k < m; k++)
+        if (P.rb_lens[k] > mut_max_len_) return false;  // no feed (~0u), or not the mutator's chunk
+      stats_.readback_tcs += m;
+    }
+  }
   const size_t base = Out.size();
   Out.resize(base + finished.size());
   HostPool::Get().For(finished.size(), 2048, [&](size_t i) {
@@ -2088,6 +2152,11 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
       Out[base + i] = StreamResult_t{tag_[l], nullptr, ex[l - first].icount};
     } else {
       Out[base + i] = StreamResult_t{tag_[l], &lres_[l]};
+      if (mut_on_ && ordered_[l]) {  // its place in the read-back list (ascending, as finished is)
+        const size_t k = (size_t)(std::lower_bound(P.rb_lanes.begin(), P.rb_lanes.end(), l) - P.rb_lanes.begin());
+        Out[base + i].tc = P.rb_bytes.data() + k * std::max<uint32_t>(mut_max_len_, 1);
+        Out[base + i].tc_size = P.rb_lens[k];
+      }
     }
     busy_[l] = 0;  // not runnable until refilled (a finished lane keeps its exit status)
   }, finished.size() >= 8192);
@@ -2136,10 +2205,10 @@ std::string GpuBackend_t::StatsJson() const {
   r.pop_back();
   snprintf(b, sizeof(b), ",\"up_prep_ms\":%.3f,\"up_regs_ms\":%.3f,\"up_apply_ms\":%.3f,\"up_feed_ms\":%.3f,"
            "\"restore_dev_ms\":%.3f,\"out_ms\":%.3f,\"fresh_ms\":%.3f,\"occ_ms\":%.3f,\"harvest_ms\":%.3f,"
-           "\"prepared\":%llu,\"device_attrib\":%d",
+           "\"prepared\":%llu,\"device_attrib\":%d,\"mutate_dev_ms\":%.3f,\"readback_tcs\":%llu",
            stats_.up_prep_ms, stats_.up_regs_ms, stats_.up_apply_ms, stats_.up_feed_ms, stats_.restore_dev_ms,
            stats_.out_ms, stats_.fresh_ms, stats_.occ_ms, stats_.harvest_ms, (unsigned long long)stats_.prepared,
-           device_attrib_ ? 1 : 0);
+           device_attrib_ ? 1 : 0, stats_.mutate_dev_ms, (unsigned long long)stats_.readback_tcs);
   r += b;
   {  // the spill pool's counters (zero without one)
     wtfgpu_spill_stats_t sp{};

@@ -49,6 +49,8 @@ struct BatchStats {
   // upload split: write-record preparation on the host, register upload,
   // memory-write apply, feed upload; device restore within restore_ms
   double up_prep_ms = 0, up_regs_ms = 0, up_apply_ms = 0, up_feed_ms = 0, restore_dev_ms = 0;
+  double mutate_dev_ms = 0;     // --device-mutate: wtfgpu_mutate_feed_lanes calls (host time; the kernel is asynchronous)
+  uint64_t readback_tcs = 0;    // --device-mutate: testcases read back from the device
   double out_ms = 0, fresh_ms = 0, occ_ms = 0, harvest_ms = 0;  // streaming: result hand-over, refill list, slice list, whole harvest
   // streaming harvest split: per-lane byte counters, coverage logs, attribution
   double bytes_ms = 0, covlog_ms = 0, attrib_ms = 0;
@@ -106,6 +108,13 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   // streaming (continuous batching): see Executor_t
   bool CanStream() const override { return true; }
   bool TakesPrepared() const override { return feed_action_ || insert_action_; }
+  // --device-mutate: ordered testcases are made by wtfgpu_mutate_feed_lanes at
+  // the refill, and the harvest reads back (wtfgpu_read_feed_lanes) the ones
+  // whose result is not the common counted one
+  bool HasDeviceMutator() const override { return true; }
+  bool MutatesOnDevice() const override { return mut_on_; }
+  bool SetDeviceMutate(uint64_t Seed, uint32_t MaxLen, uint64_t MaxEntries, uint64_t MaxBytes) override;
+  bool DeviceCorpusAdd(const uint8_t *P, size_t N) override;
   uint32_t FreeLanes() const override;
   bool StreamStep(const Target_t &Target, const std::vector<StreamTestcase_t> &In, uint64_t Slice,
                   std::vector<StreamResult_t> &Out, ModuleSlots *Slots, size_t *Taken) override;
@@ -303,6 +312,10 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
     uint64_t ex_cap = 0;
     uint8_t *pin = nullptr;
     uint64_t pin_cap = 0;
+    // --device-mutate: the testcases the last harvest read back (lens, bytes
+    // at a stride of mut_max_len_), valid until the part's next harvest
+    std::vector<uint32_t> rb_lanes, rb_lens;
+    std::vector<uint8_t> rb_bytes;
     // the slice's read-back queued behind it (wtfgpu_prefetch_results /
     // _coverage), pinned: byte and dirty-page counts, StopWithArgs
     // arguments, the coverage entry count
@@ -347,6 +360,14 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   uint64_t tenet_cap_ = 0;                       // Tenet stream bytes per lane (EnableTenet)
   std::unordered_map<uint64_t, BreakpointAction_t::ArgsResult_t> args_results_;  // StopWithArgs, by gva
   bool feed_action_ = false;                     // a Feed action is on the device
+  // --device-mutate: on, the stream's seed and longest testcase; which lanes
+  // hold an ordered testcase; the refill's order lists
+  bool mut_on_ = false;
+  uint64_t mut_seed_ = 0;
+  uint32_t mut_max_len_ = 0;
+  std::vector<uint8_t> ordered_;
+  std::vector<uint32_t> mut_lanes_, mut_nc_;
+  std::vector<uint64_t> mut_idx_;
   bool insert_action_ = false;                   // the declared insert is on the device (wtfgpu_set_insert)
   int upload_feed(uint32_t n);                   // lanes [0, n)
   std::unordered_set<uint64_t> aggregate_;

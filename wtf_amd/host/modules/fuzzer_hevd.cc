@@ -44,13 +44,15 @@ TestcaseResult_t BugCheckResult(const uint64_t *A) {
   return Crash_t(std::move(Name));
 }
 
+constexpr size_t kMaxIoctlBuffer = 1024;  // InsertTestcase, PrepareInsert and the declared insert's bound
+
 bool InsertTestcase(const uint8_t *Buffer, const size_t BufferSize) {
   if (BufferSize < sizeof(uint32_t)) return true;
   uint32_t Ioctl;
   memcpy(&Ioctl, Buffer, sizeof(Ioctl));
   const size_t IoctlBufferSize = BufferSize - sizeof(uint32_t);
   const uint8_t *IoctlBuffer = Buffer + sizeof(uint32_t);
-  if (IoctlBufferSize > 1024) return false;
+  if (IoctlBufferSize > kMaxIoctlBuffer) return false;
   // the declared form below (Init): a backend that applies it on the device
   // takes the whole testcase
   if (g_Backend->SetInsert(Buffer, BufferSize)) return true;
@@ -67,14 +69,15 @@ bool InsertTestcase(const uint8_t *Buffer, const size_t BufferSize) {
 // declared insert of the whole testcase
 PreparedInsert_t PrepareInsert(const uint8_t *, const size_t BufferSize, std::vector<uint8_t> &) {
   if (BufferSize < sizeof(uint32_t)) return PreparedInsert_t::Nothing;
-  if (BufferSize - sizeof(uint32_t) > 1024) return PreparedInsert_t::Failed;
+  if (BufferSize - sizeof(uint32_t) > kMaxIoctlBuffer) return PreparedInsert_t::Failed;
   return PreparedInsert_t::Insert;
 }
 
 bool Init(const Options_t &, const CpuState_t &) {
   // InsertTestcase as data (device-side on the gpu backend)
   g_Backend->DeclareInsert(
-      InsertAction_t::HeadAndPayload(Registers_t::Rdx, Registers_t::R8, Registers_t::R9, /*LenArg=*/5));
+      InsertAction_t::HeadAndPayload(Registers_t::Rdx, Registers_t::R8, Registers_t::R9, /*LenArg=*/5,
+                                     /*MaxPayload=*/(uint32_t)kMaxIoctlBuffer));
   const Gva_t Rip = Gva_t(g_Backend->Rip());
   const Gva_t AfterCall = Rip + Gva_t(6);
   if (!g_Backend->SetBreakpoint(

@@ -259,6 +259,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     else if (a == "--full-coverage") O.full_coverage = true;
     else if (a == "--edges") O.edges = true;
     else if (a == "--device-attrib") O.device_attrib = true;
+    else if (a == "--device-mutate") O.device_mutate = true;
     else if (a == "--trace-path") O.trace_path = next("--trace-path");
     else if (a == "--trace-type") O.trace_type = next("--trace-type");
     else if (a == "--trace-cap") O.trace_cap = (uint32_t)strtoul(next("--trace-cap"), nullptr, 0);
@@ -286,6 +287,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     }
   }
   if (const char *e = getenv("WTF_RCCL_FORCE")) O.rccl_force = O.rccl_force || atoi(e) != 0;
+  if (const char *e = getenv("WTFGPU_DEVICE_MUTATE")) O.device_mutate = O.device_mutate || atoi(e) != 0;
   if (O.world < 1 || O.rank < 0 || O.rank >= O.world) {
     fprintf(stderr, "--rank must be in [0, --world)\n");
     return false;
@@ -294,11 +296,17 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     fprintf(stderr, "master needs --address and --nodes >= 1\n");
     return false;
   }
+  if (O.device_mutate && O.mode != "run" &&
+      (O.mode == "master" || !O.address.empty() || O.world > 1 || !O.module_so.empty())) {
+    fprintf(stderr, "--device-mutate is for one in-process fuzz session: not with master, --address, --world > 1 or "
+                    "--module-so\n");
+    return false;
+  }
   if (O.name.empty() || O.target.empty()) {
     fprintf(stderr, "usage: [run|fuzz|master] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
                     "       [--lanes n] [--overlay-pages k] [--spill-pages s [--spill-lane-max x]] [--runs n] [--seconds s] [--seed s] [--full-coverage]\n"
                     "       [--serial-mutation] [--slice-steps s] [--regroup-steps r] [--rank r --world n [--exchange host:port | --nccl-id-file f]]\n"
-                    "       [--address tcp://ip:port|unix://path [--batched] [--nodes k]] [--edges] [--device-attrib]\n"
+                    "       [--address tcp://ip:port|unix://path [--batched] [--nodes k]] [--edges] [--device-attrib] [--device-mutate]\n"
                     "       [--trace-path dir [--trace-type rip|cov|tenet] [--trace-cap n] [--tenet-cap bytes]] [--module-so m.so] [--serial]\n");
     return false;
   }
@@ -616,7 +624,7 @@ int RunnerMain(const RunnerOptions &O, Executor_t &Exec, const Options_t &Opts, 
   }
   FuzzSession F(O, Exec, *Target, Slots, X);
   if (!F.Start()) {
-    printf("Nothing to run: empty corpus and no inputs\n");
+    if (!F.Refused()) printf("Nothing to run: empty corpus and no inputs\n");
     return 1;
   }
   const bool Shards = X && X->Exchanging();
@@ -726,6 +734,10 @@ bool FuzzSession::Start() {
   }
   t0_ = Clock::now();
   stream_ = O_.slice && Exec_.CanStream();
+  if (O_.device_mutate && !StartDeviceMutate()) {
+    Refused_ = true;
+    return false;
+  }
   // inserts prepared where the testcases are made (not for per-lane module
   // copies: each lane calls its own copy's InsertTestcase)
   if (stream_ && Exec_.TakesPrepared() && !Slots_.Instances() && !getenv("WTF_NO_PREPARED_INSERT"))
@@ -736,6 +748,50 @@ bool FuzzSession::Start() {
   }
   Batch_ = MakeBatch(Budget(Exec_.Lanes()));
   return !Batch_.empty();
+}
+
+// --device-mutate: what it cannot serve is refused here, with a message,
+// before any lane runs. The stream's longest testcase is the least of
+// --max_len, the feed region and what the module's insert accepts.
+bool FuzzSession::StartDeviceMutate() {
+  if (Target_.CreateMutator != LibfuzzerMutator_t::Create) {
+    printf("--device-mutate: target %s has a mutator of its own; the device mutator replaces the default one only\n",
+           O_.name.c_str());
+    return false;
+  }
+  const std::optional<InsertAction_t> &Ins = InsertAction_t::Declared();
+  if (!Ins) {
+    printf("--device-mutate: target %s declares no insert (InsertAction_t)\n", O_.name.c_str());
+    return false;
+  }
+  uint64_t Max = std::min<uint64_t>(O_.max_len, kDeviceMutateMaxLen);
+  if (Ins->MaxPayload) Max = std::min<uint64_t>(Max, 4ull + Ins->MaxPayload);
+  DevMaxLen_ = (uint32_t)Max;
+  if (Exec_.HasDeviceMutator()) {  // it mutates on its device, in streaming runs
+    if (!stream_) {
+      printf("--device-mutate needs a streaming run on this executor (--slice-steps != 0)\n");
+      return false;
+    }
+    if (!Exec_.SetDeviceMutate(O_.seed, DevMaxLen_, DevCorpus_.MaxEntries, DevCorpus_.MaxBytes)) {
+      printf("--device-mutate: the executor does not apply target %s's insert on the device\n", O_.name.c_str());
+      return false;
+    }
+  }
+  DevOnDevice_ = Exec_.MutatesOnDevice();
+  return true;
+}
+
+// A corpus entry the session keeps, for the device mutator too (in account order)
+void FuzzSession::DevCorpusAdd(const uint8_t *Tc, size_t Size) {
+  if (!O_.device_mutate) return;
+  if (!DevCorpus_.Add(Tc, Size)) {
+    DevDropped_++;
+    return;
+  }
+  if (DevOnDevice_ && !Exec_.DeviceCorpusAdd(Tc, Size)) {
+    printf("--device-mutate: the device corpus refused an entry the host copy took\n");
+    exit(1);
+  }
 }
 
 void FuzzSession::Adopt(TcBatch &&B) {
@@ -787,7 +843,25 @@ TcBatch FuzzSession::MakeBatch(uint64_t n) {
   // a read-only view of the corpus (deterministic for a seed whatever the
   // thread count; the corpus does not change while the batch is built)
   const size_t Need = n - Made;
-  if (Corpus_.Size() && Need >= kParMutateMin && !O_.serial_mutation) {
+  if (O_.device_mutate && DevCorpus_.Count()) {
+    // the device mutator's stream: testcase NextIndex_ over the corpus as it
+    // stands; as an order for an executor that mutates on the device, else
+    // made here from the same definition. Neither the mutation workers nor
+    // the host mutator run.
+    const uint32_t NC = (uint32_t)DevCorpus_.Count();
+    Batch.push_back(NewArena());
+    TcArena &A = *Batch.back();
+    std::vector<uint8_t> Buf(std::max<uint32_t>(DevMaxLen_, 1));
+    for (; Made < n; Made++) {
+      const uint64_t Index = NextIndex_++;
+      if (DevOnDevice_) {
+        A.AddOrder(Index, NC);
+      } else {
+        A.Add(Buf.data(), DeviceMutate(O_.seed, Index, DevCorpus_, NC, DevMaxLen_, Buf.data()));
+        if (Prepare_) A.Prepare(Prepare_, PrepScratch_);
+      }
+    }
+  } else if (Corpus_.Size() && Need >= kParMutateMin && !O_.serial_mutation) {
     const size_t Chunks = (Need + kMutateChunk - 1) / kMutateChunk;
     std::vector<uint64_t> Seeds(Chunks);
     for (uint64_t &S : Seeds) S = Rng_();
@@ -947,6 +1021,11 @@ bool FuzzSession::StreamStep(bool Done) {
           const TcRef R{A, G.B + (uint32_t)(i - Taken_[r].second)};
           Slot_[tag] = R;
           StreamTestcase_t T{R.data(), R.size(), tag};
+          if (R.ordered()) {
+            T.ordered = true;
+            T.index = A->Orders[R.I].index;
+            T.ncorpus = A->Orders[R.I].ncorpus;
+          }
           if (prep) {
             T.prep = R.prep();
             T.prep_data = R.prep_data();
@@ -1017,6 +1096,7 @@ void FuzzSession::ReleaseArena(TcArena *A) {
   Own->Prep.clear();
   Own->PrepData.clear();
   Own->PrepOff.assign(1, 0);
+  Own->Orders.clear();
   std::lock_guard<std::mutex> g(ArenaPoolMu_);
   if (ArenaPool_.size() < 512) ArenaPool_.push_back(std::move(Own));
 }
@@ -1093,6 +1173,11 @@ bool FuzzSession::AccountStep(std::vector<StreamResult_t> &Out) {
       const StreamResult_t &F = Out[E.first];
       serial++;
       if (!F.r) Plain.icount = F.icount;
+      if (E.second.ordered()) {  // made on the device: the executor read its bytes back
+        if (!F.r || (!F.tc && F.tc_size)) return false;
+        Account(F.tc, F.tc_size, *F.r, false);
+        continue;
+      }
       Account(E.second.data(), E.second.size(), F.r ? *F.r : Plain, false);
     }
   S_.execs += n - serial;
@@ -1153,7 +1238,7 @@ void FuzzSession::Account(const uint8_t *Tc, size_t Size, const LaneResult &L, b
       Mutator_->OnNewCoverage(Tcase);
       LastNewCov_.assign((const char *)Tc, Size);
       HaveNewCov_ = true;
-      Corpus_.SaveTestcase(L.result, std::move(Tcase));
+      if (Corpus_.SaveTestcase(L.result, std::move(Tcase))) DevCorpusAdd(Tc, Size);
     }
     S_.newcov_ms += secs_since(tn) * 1e3;
   }
@@ -1251,6 +1336,7 @@ std::string FuzzSession::SummaryJson() const {
            "\"merges\":%llu,\"merged_map_bytes\":%llu,"
            "\"merge_ms\":%.3f,\"produce_wait_ms\":%.3f,\"account_ms\":%.3f,\"make_ms\":%.3f,\"step_ms\":%.3f,\"fill_ms\":%.3f,"
            "\"newcov_ms\":%.3f,\"crashsave_ms\":%.3f,\"call_ms\":%.3f,\"cpu_s\":%.3f,\"mutate_cpu_ms\":%.3f,"
+           "\"device_mutate\":%d,\"device_corpus_dropped\":%llu,"
            "\"backend\":",
            O_.name.c_str(), Exec_.Lanes(), X_ ? X_->Rank() : 0, X_ ? X_->World() : 1,
            (unsigned long long)S_.batches, (unsigned long long)S_.execs, (unsigned long long)S_.retired, Wall,
@@ -1260,7 +1346,7 @@ std::string FuzzSession::SummaryJson() const {
            (unsigned long long)S_.error_retired, (unsigned long long)S_.merged_rips,
            (unsigned long long)S_.merges, (unsigned long long)S_.merged_map_bytes, S_.merge_ms, S_.produce_wait_ms,
            S_.account_ms, S_.make_ms, S_.step_ms, S_.fill_ms, S_.newcov_ms, S_.crashsave_ms, S_.call_ms, ProcessCpuSeconds(),
-           MutateCpuNs_.load() * 1e-6);
+           MutateCpuNs_.load() * 1e-6, O_.device_mutate ? 1 : 0, (unsigned long long)DevDropped_);
   return std::string(b) + Exec_.StatsJson() + "}";
 }
 

@@ -51,6 +51,11 @@ struct StreamTestcase_t {
   PreparedInsert_t prep = PreparedInsert_t::Call;
   const uint8_t *prep_data = nullptr;
   size_t prep_size = 0;
+  // --device-mutate on an executor that mutates on the device: no bytes; the
+  // testcase is (index, ncorpus) of the session's stream (csrc/engine_mutate.h)
+  bool ordered = false;
+  uint64_t index = 0;
+  uint32_t ncorpus = 0;
 };
 // A finished testcase: its tag and its result, which stays in the executor's
 // storage and is valid until the executor's next StreamStep (no per-result
@@ -62,6 +67,10 @@ struct StreamResult_t {
   uint64_t tag;
   LaneResult *r;
   uint64_t icount = 0;  // with r == nullptr
+  // an ordered testcase (StreamTestcase_t::ordered) with r != nullptr: its
+  // bytes, read back from the device; valid as long as r is
+  const uint8_t *tc = nullptr;
+  size_t tc_size = 0;
 };
 
 // A backend that runs many testcases per call (GpuBackend_t; the oracle twin
@@ -77,6 +86,18 @@ class Executor_t {
   virtual bool CanStream() const { return false; }
   // StreamStep uses prepared inserts (StreamTestcase_t::prep)
   virtual bool TakesPrepared() const { return false; }
+  // --device-mutate: true = this executor makes ordered testcases
+  // (StreamTestcase_t::ordered) itself, from the corpus entries it was given
+  // with DeviceCorpusAdd, and returns the bytes of the ones the session keeps
+  // (StreamResult_t::tc); false (default) = the session materialises every
+  // order on the host, from the same definition (device_mutator.cc).
+  virtual bool HasDeviceMutator() const { return false; }  // it can (a device with the engine's mutator)
+  virtual bool MutatesOnDevice() const { return false; }
+  // Seed and longest testcase of the stream; false = it cannot (no declared insert on the device, ...)
+  virtual bool SetDeviceMutate(uint64_t /*Seed*/, uint32_t /*MaxLen*/, uint64_t /*MaxEntries*/, uint64_t /*MaxBytes*/) {
+    return false;
+  }
+  virtual bool DeviceCorpusAdd(const uint8_t *, size_t) { return false; }
   virtual uint32_t FreeLanes() const { return 0; }
   virtual bool StreamStep(const Target_t &, const std::vector<StreamTestcase_t> &, uint64_t,
                           std::vector<StreamResult_t> &, ModuleSlots *, size_t *Taken) {
@@ -210,6 +231,9 @@ struct RunnerOptions {
   bool full_coverage = false;
   bool edges = false;        // --edges: branch edges join the coverage (RecordEdge)
   bool device_attrib = false;  // --device-attrib: new coverage attributed in lane order on the GPU
+  // --device-mutate (also WTFGPU_DEVICE_MUTATE=1): the device mutator's stream
+  // (csrc/engine_mutate.h) instead of the target's host mutator
+  bool device_mutate = false;
   std::string trace_path;    // run: --trace-path dir (one <input>.trace per input, subcommands.cc:52-74)
   std::string trace_type = "rip";  // run: --trace-type rip | cov | tenet (wtf.cc:197-200)
   uint32_t trace_cap = 1u << 20;   // run: rips kept per testcase
@@ -271,6 +295,16 @@ struct TcArena {
   std::vector<PreparedInsert_t> Prep;
   std::vector<uint8_t> PrepData;
   std::vector<uint64_t> PrepOff{0};
+  // --device-mutate: an arena of orders holds no bytes; testcase I is Orders[I]
+  struct Order {
+    uint64_t index;
+    uint32_t ncorpus;
+  };
+  std::vector<Order> Orders;
+  void AddOrder(uint64_t Index, uint32_t NCorpus) {
+    Orders.push_back(Order{Index, NCorpus});
+    Off.push_back(Data.size());
+  }
   void Add(const void *P, size_t N) {
     const uint8_t *B = (const uint8_t *)P;
     Data.insert(Data.end(), B, B + N);
@@ -295,10 +329,27 @@ struct TcRef {
   uint32_t I = 0;
   const uint8_t *data() const { return A->Ptr(I); }
   size_t size() const { return A->Len(I); }
+  bool ordered() const { return I < A->Orders.size(); }
   PreparedInsert_t prep() const { return I < A->Prep.size() ? A->Prep[I] : PreparedInsert_t::Call; }
   const uint8_t *prep_data() const { return A->PrepData.data() + A->PrepOff[I]; }
   size_t prep_size() const { return A->PrepOff[I + 1] - A->PrepOff[I]; }
 };
+
+// --device-mutate on the host (device_mutator.cc): the corpus laid out as the
+// device arena (wtfgpu_corpus_add) and the stream's definition
+// (csrc/engine_mutate.h) built for the host, for executors that do not mutate
+// on the device. Add refuses what the arena's bounds refuse.
+struct DeviceCorpus {
+  std::vector<uint8_t> Bytes;
+  std::vector<uint64_t> Off{0};
+  uint64_t MaxEntries = 1u << 16, MaxBytes = 64ull << 20;
+  size_t Count() const { return Off.size() - 1; }
+  bool Add(const uint8_t *P, size_t N);
+};
+// testcase `Index` of the stream `Seed` over the first NCorpus entries, into Out (MaxLen bytes of room); its size
+size_t DeviceMutate(uint64_t Seed, uint64_t Index, const DeviceCorpus &C, uint32_t NCorpus, uint32_t MaxLen,
+                    uint8_t *Out);
+constexpr uint32_t kDeviceMutateMaxLen = 16380;  // WTFGPU_FEED_STRIDE - 4
 
 // The fuzz loop of one node / shard, one batch per Step(): an in-process
 // master (corpus, mutator, crash saving: server.h:629-886) feeding the
@@ -329,7 +380,8 @@ class FuzzSession {
   FuzzSession(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, ModuleSlots &Slots,
               CoverageExchange_t *X);
   ~FuzzSession();
-  bool Start();      // corpus inputs + the first batch; false = nothing to run
+  bool Start();      // corpus inputs + the first batch; false = nothing to run, or refused
+  bool Refused() const { return Refused_; }  // Start printed why (--device-mutate's refusals)
   bool Step();       // one batch; false = the executor failed
   bool Done() const;
   // shards (world > 1): every shard was done as of the last merge absorbed
@@ -378,6 +430,18 @@ class FuzzSession {
   std::vector<std::string> Pending_;
   TcBatch Batch_;                // batch mode: the batch in the lanes
   std::vector<TcRef> BatchRefs_;
+  // --device-mutate: the corpus as the device mutator reads it (every entry
+  // the session keeps, in account order, within the arena's bounds), the next
+  // testcase's index, the effective max_len, entries the arena had no room for
+  DeviceCorpus DevCorpus_;
+  uint64_t NextIndex_ = 0;
+  uint32_t DevMaxLen_ = 0;
+  uint64_t DevDropped_ = 0;
+  bool Refused_ = false;
+  bool DevOnDevice_ = false;  // the executor mutates (orders); else the session materialises
+  std::vector<uint8_t> PrepScratch_;  // PrepareInsert's scratch for materialised testcases
+  bool StartDeviceMutate();   // the refusals; false = a message was printed
+  void DevCorpusAdd(const uint8_t *Tc, size_t Size);
   std::string LastNewCov_;  // the testcase last passed to Mutator_->OnNewCoverage
   bool HaveNewCov_ = false;
   std::future<TcBatch> Next_;

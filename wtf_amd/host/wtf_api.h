@@ -308,13 +308,26 @@ struct InsertAction_t {
   Registers_t PtrReg = Registers_t::R8;
   Registers_t LenReg = Registers_t::R9;
   uint32_t LenArg = 0;
+  // The longest payload the module's InsertTestcase accepts (0: none stated).
+  // --device-mutate makes no testcase longer than the head plus this, so the
+  // device mutator never makes one whose insert the module would refuse.
+  uint32_t MaxPayload = 0;
+  // The module's last declaration, whatever the backend answered to
+  // DeclareInsert (the twin applies none): the runner reads it for
+  // --device-mutate.
+  static std::optional<InsertAction_t> &Declared() {
+    static std::optional<InsertAction_t> D;
+    return D;
+  }
   static InsertAction_t HeadAndPayload(const Registers_t Head, const Registers_t Ptr, const Registers_t Len,
-                                       const uint32_t LenArg) {
+                                       const uint32_t LenArg, const uint32_t MaxPayload = 0) {
     InsertAction_t A;
     A.HeadReg = Head;
     A.PtrReg = Ptr;
     A.LenReg = Len;
     A.LenArg = LenArg;
+    A.MaxPayload = MaxPayload;
+    Declared() = A;
     return A;
   }
 };
