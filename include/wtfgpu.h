@@ -379,6 +379,46 @@ int wtfgpu_mutate_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n,
  * server.h:629-714). */
 int wtfgpu_read_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t *lens, uint8_t *bytes,
                            uint64_t stride);
+/* Device packet mutator (`wtfgpu fuzz --device-packets`): the same plumbing
+ * for targets whose testcase is a list of packets and whose lanes consume it
+ * as a feed of chunks (u32 Size, u32 Command, u16 Id, u16 BodySize, Body; Size
+ * = 8 + the body's bytes). The generator is csrc/engine_mutate_packets.h,
+ * which documents the stream; it is not the reference's.
+ *
+ * wtfgpu_corpus_add_feed: appends a feed as a corpus entry, in the engine's
+ * own indexed layout (packet count, chunk offsets, chunks). The feed is
+ * validated here and nowhere else: the chunks must tile `len` exactly, every
+ * Size be 8 or more, and len be at most WTFGPU_FEED_STRIDE; otherwise
+ * WTFGPU_ERR_INVALID and the arena is unchanged. WTFGPU_ERR_FULL as
+ * wtfgpu_corpus_add. An arena holds one kind of entry, fixed by its first
+ * add: mixing wtfgpu_corpus_add and wtfgpu_corpus_add_feed gives
+ * WTFGPU_ERR_STATE, as does wtfgpu_mutate_feed_lanes on an arena of feeds and
+ * wtfgpu_mutate_packets_lanes on one of byte buffers. */
+typedef struct wtfgpu_packet_params {
+  uint32_t gen_max_packets;    /* Generate: 1..gen_max_packets packets (at most 64) */
+  uint32_t gen_commands;       /* Command in [0, gen_commands) */
+  uint32_t gen_max_body;       /* body of 0..gen_max_body zero bytes */
+  uint32_t flip_one_in;        /* one BodySize in flip_one_in gets a bit flipped */
+  uint32_t insert_max_packets; /* insert-copy leaves a longer list alone */
+} wtfgpu_packet_params_t;
+int wtfgpu_corpus_add_feed(wtfgpu_ctx *ctx, const uint8_t *feed, uint64_t len, uint32_t *index);
+/* Lane lanes[i] gets, as its whole feed, testcase indices[i] of the packet
+ * stream `seed` over the first ncorpus[i] corpus entries; its read position
+ * and end are set as wtfgpu_set_feed_lanes sets them, and a feed of zero bytes
+ * is a feed. No result is longer than WTFGPU_FEED_STRIDE. Asynchronous on the
+ * current queue; no caller's buffer is read after it returns.
+ * WTFGPU_ERR_INVALID, before anything is queued, for an ncorpus[i] of 0 or
+ * above the entries added, a lane outside the context, no arena, or params out
+ * of range (a count of 0, gen_max_packets above 64, or gen_max_packets * (12 +
+ * gen_max_body) above WTFGPU_FEED_STRIDE). */
+int wtfgpu_mutate_packets_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint64_t seed,
+                                const uint64_t *indices, const uint32_t *ncorpus,
+                                const wtfgpu_packet_params_t *params);
+/* As wtfgpu_read_feed_lanes, but the lane's whole feed, every chunk, from its
+ * region's first byte to the feed's end (the feed stays in place while the
+ * lane consumes it, until the lane's next feed). */
+int wtfgpu_read_whole_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t *lens, uint8_t *bytes,
+                                 uint64_t stride);
 /* New-coverage sets of a lane list (as wtfgpu_read_coverage); a call whose
  * cap covers the count also empties those lanes' sets (cap = 0 with an empty
  * result included). */

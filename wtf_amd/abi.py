@@ -81,7 +81,13 @@ class Insert(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("head_reg", "ptr_reg", "len_reg", "len_arg")]
 
 
-ERR_INVALID, ERR_FULL = -1, -7
+class PacketParams(C.Structure):
+    """wtfgpu_packet_params_t"""
+    _fields_ = [(k, C.c_uint32) for k in ("gen_max_packets", "gen_commands", "gen_max_body", "flip_one_in",
+                                          "insert_max_packets")]
+
+
+ERR_INVALID, ERR_STATE, ERR_FULL = -1, -5, -7
 FEED_STRIDE = 16384  # WTFGPU_FEED_STRIDE: a testcase chunk is at most FEED_STRIDE - 4 bytes
 
 SEG_ORDER = ["es", "cs", "ss", "ds", "fs", "gs", "tr", "ldtr"]
@@ -191,6 +197,10 @@ def load_hip_library(path: str = LIB_PATH) -> C.CDLL:
         "wtfgpu_corpus_add": ([P, C.c_char_p, U64, C.POINTER(U32)], C.c_int),
         "wtfgpu_mutate_feed_lanes": ([P, C.POINTER(U32), U32, U64, C.POINTER(U64), C.POINTER(U32), U32], C.c_int),
         "wtfgpu_read_feed_lanes": ([P, C.POINTER(U32), U32, C.POINTER(U32), P, U64], C.c_int),
+        "wtfgpu_corpus_add_feed": ([P, C.c_char_p, U64, C.POINTER(U32)], C.c_int),
+        "wtfgpu_mutate_packets_lanes": ([P, C.POINTER(U32), U32, U64, C.POINTER(U64), C.POINTER(U32),
+                                         C.POINTER(PacketParams)], C.c_int),
+        "wtfgpu_read_whole_feed_lanes": ([P, C.POINTER(U32), U32, C.POINTER(U32), P, U64], C.c_int),
     }
     for name, (args, ret) in sig.items():
         fn = getattr(lib, name)

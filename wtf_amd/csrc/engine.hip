@@ -125,6 +125,9 @@ struct wtfgpu_ctx {
   u64 *d_corpus_off = nullptr;
   u64 corpus_max_entries = 0, corpus_max_bytes = 0;
   std::vector<u64> corpus_off;
+  // what the arena holds, fixed by its first add: byte buffers
+  // (wtfgpu_corpus_add) or indexed feeds (wtfgpu_corpus_add_feed)
+  enum CorpusKind : u32 { kCorpusEmpty, kCorpusBytes, kCorpusFeeds } corpus_kind = kCorpusEmpty;
   // coverage
   u64 *d_codekeys = nullptr;
   u32 *d_codeslot = nullptr;
@@ -1090,6 +1093,7 @@ int wtfgpu_corpus_alloc(wtfgpu_ctx *c, uint64_t max_entries, uint64_t max_bytes)
   dfree(c->d_corpus_off);
   c->corpus_max_entries = c->corpus_max_bytes = 0;
   c->corpus_off.clear();
+  c->corpus_kind = wtfgpu_ctx::kCorpusEmpty;
   if (max_entries == 0) return WTFGPU_OK;
   if (dalloc(&c->d_corpus, max_bytes) || dalloc(&c->d_corpus_off, max_entries + 1)) {
     dfree(c->d_corpus);
@@ -1105,6 +1109,7 @@ int wtfgpu_corpus_alloc(wtfgpu_ctx *c, uint64_t max_entries, uint64_t max_bytes)
 
 int wtfgpu_corpus_add(wtfgpu_ctx *c, const uint8_t *bytes, uint64_t len, uint32_t *index) {
   if (!c || !c->d_corpus || (len && !bytes)) return WTFGPU_ERR_INVALID;
+  if (c->corpus_kind == wtfgpu_ctx::kCorpusFeeds) return WTFGPU_ERR_STATE;
   const u64 count = c->corpus_off.size() - 1, used = c->corpus_off.back();
   if (count >= c->corpus_max_entries || len > c->corpus_max_bytes - used) return WTFGPU_ERR_FULL;
   HIPCHK(hipSetDevice(c->device));
@@ -1115,6 +1120,29 @@ int wtfgpu_corpus_add(wtfgpu_ctx *c, const uint8_t *bytes, uint64_t len, uint32_
   const u64 end = used + len;
   HIPCHK(hipMemcpy(c->d_corpus_off + count + 1, &end, 8, hipMemcpyHostToDevice));
   c->corpus_off.push_back(end);
+  c->corpus_kind = wtfgpu_ctx::kCorpusBytes;
+  if (index) *index = (u32)count;
+  return WTFGPU_OK;
+}
+
+int wtfgpu_corpus_add_feed(wtfgpu_ctx *c, const uint8_t *feed, uint64_t len, uint32_t *index) {
+  if (!c || !c->d_corpus || (len && !feed)) return WTFGPU_ERR_INVALID;
+  // the only gate: k_mutate_packets trusts every offset of an entry
+  const int64_t packets = wtfpkt::entry_packets(feed, len, WTFGPU_FEED_STRIDE);
+  if (packets < 0) return WTFGPU_ERR_INVALID;
+  if (c->corpus_kind == wtfgpu_ctx::kCorpusBytes) return WTFGPU_ERR_STATE;
+  const u64 count = c->corpus_off.size() - 1, used = c->corpus_off.back();
+  const u64 bytes = wtfpkt::entry_bytes((u64)packets, len);
+  if (count >= c->corpus_max_entries || bytes > c->corpus_max_bytes - used) return WTFGPU_ERR_FULL;
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<u8> entry(bytes);
+  wtfpkt::entry_write(feed, len, (u64)packets, entry.data());
+  // blocking copies, as wtfgpu_corpus_add; entries stay 4-aligned (every size is a multiple of 4)
+  HIPCHK(hipMemcpy(c->d_corpus + used, entry.data(), bytes, hipMemcpyHostToDevice));
+  const u64 end = used + bytes;
+  HIPCHK(hipMemcpy(c->d_corpus_off + count + 1, &end, 8, hipMemcpyHostToDevice));
+  c->corpus_off.push_back(end);
+  c->corpus_kind = wtfgpu_ctx::kCorpusFeeds;
   if (index) *index = (u32)count;
   return WTFGPU_OK;
 }
@@ -1130,6 +1158,7 @@ int wtfgpu_mutate_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, u
     for (u32 i = 0; i < n; i++) bad |= (u32)(ncorpus[i] == 0) | (u32)(ncorpus[i] > count);
     if (bad) return WTFGPU_ERR_INVALID;
   }
+  if (c->corpus_kind == wtfgpu_ctx::kCorpusFeeds) return WTFGPU_ERR_STATE;
   if (n == 0) return WTFGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   if (int rc = feed_regions(c)) return rc;
@@ -1169,6 +1198,60 @@ int wtfgpu_read_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uin
                                              (u32 *)(S + s[0].off), S + s[1].off, stride);
   HIPCHK(hipGetLastError());
   // gathered on the device, so the copy back is the listed lanes' bytes only; one wait
+  HIPCHK(hipMemcpyAsync(lens, S + s[0].off, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
+  if (stride) return read_back(c, bytes, s[1]);
+  HIPCHK(hipStreamSynchronize(c->q->stream));
+  return WTFGPU_OK;
+}
+
+int wtfgpu_mutate_packets_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint64_t seed,
+                                const uint64_t *indices, const uint32_t *ncorpus,
+                                const wtfgpu_packet_params_t *params) {
+  if (!c || !c->d_gpr || !c->d_corpus || !params || (n && (!lanes || !indices || !ncorpus)) ||
+      !lane_list_in_range(c, lanes, n))
+    return WTFGPU_ERR_INVALID;
+  const wtfpkt::Params q{params->gen_max_packets, params->gen_commands,       params->gen_max_body,
+                         params->flip_one_in,     params->insert_max_packets, WTFGPU_FEED_STRIDE};
+  if (!wtfpkt::params_valid(q)) return WTFGPU_ERR_INVALID;
+  {  // every order reads entries that exist: the kernel checks nothing
+    const u64 count = c->corpus_off.size() - 1;
+    u32 bad = 0;
+    for (u32 i = 0; i < n; i++) bad |= (u32)(ncorpus[i] == 0) | (u32)(ncorpus[i] > count);
+    if (bad) return WTFGPU_ERR_INVALID;
+  }
+  if (c->corpus_kind == wtfgpu_ctx::kCorpusBytes) return WTFGPU_ERR_STATE;
+  if (n == 0) return WTFGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = feed_regions(c)) return rc;
+  Side s[] = {side_in(indices, (u64)n * 8), side_in(ncorpus, (u64)n * 4)};
+  if (int rc = stage_lanes(c, Upload::Ring, lanes, n, s, 2)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_mutate_packets<<<(n + MUT_WAVES - 1) / MUT_WAVES, 64 * MUT_WAVES, 0, c->q->stream>>>(
+      c->d_feeddata, c->feed_stride, (const u32 *)S, (const u64 *)(S + s[0].off), (const u32 *)(S + s[1].off), n, seed,
+      q, c->d_corpus, c->d_corpus_off, c->d_feedpos, c->d_feedend);
+  HIPCHK(hipGetLastError());
+  c->P.feed_pos = c->d_feedpos;
+  c->P.feed_end = c->d_feedend;
+  c->P.feed_data = c->d_feeddata;
+  return WTFGPU_OK;
+}
+
+int wtfgpu_read_whole_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32_t *lens, uint8_t *bytes,
+                                 uint64_t stride) {
+  if (!c || !c->d_gpr || (n && (!lanes || !lens)) || (n && stride && !bytes) || !lane_list_in_range(c, lanes, n))
+    return WTFGPU_ERR_INVALID;
+  if (n == 0) return WTFGPU_OK;
+  if (!c->d_feedpos || c->feed_stride == 0) {  // no per-lane regions yet: no lane has a feed in one
+    for (u32 i = 0; i < n; i++) lens[i] = ~0u;
+    return WTFGPU_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  Side s[] = {side_room((u64)n * 4), side_room((u64)n * stride)};
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, s, 2)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_feed_gather_whole<<<n, 128, 0, c->q->stream>>>(c->d_feeddata, c->feed_stride, (const u32 *)S, n, c->d_feedpos,
+                                                   c->d_feedend, (u32 *)(S + s[0].off), S + s[1].off, stride);
+  HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(lens, S + s[0].off, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
   if (stride) return read_back(c, bytes, s[1]);
   HIPCHK(hipStreamSynchronize(c->q->stream));

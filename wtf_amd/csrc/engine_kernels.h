@@ -5,6 +5,7 @@
 #pragma once
 #include "engine_run.h"
 #include "engine_mutate.h"
+#include "engine_mutate_packets.h"
 
 namespace {
 
@@ -595,6 +596,101 @@ __global__ void k_feed_gather(const u8 *feed, u64 stride, const u32 *lanes, u32 
   if (threadIdx.x == 0) lens[i] = has ? (u32)len : ~0u;
   if (len > room) len = room;
   for (u64 k = threadIdx.x; k < len; k += blockDim.x) out[(u64)i * room + k] = src[4 + k];
+}
+
+// The device packet mutator (wtfgpu_mutate_packets_lanes;
+// engine_mutate_packets.h defines the stream): one wave per testcase,
+// MUT_WAVES a block, as k_mutate_feeds. The feed is the chunks themselves from
+// the region's first byte, four bytes a lane a round. Chunks are 12 + body
+// bytes long, so neither a chunk nor a source run is 4-aligned: every word is
+// composed byte by byte through the plan. The last word is zero-padded and
+// stays inside the region: size <= MaxFeed <= stride, a multiple of 4.
+//
+// A mutated testcase is a wave-uniform plan over the base entry. A generated
+// one has no base: lane p < N computes packet p's three header words from its
+// four direct draws, an exclusive prefix over the chunk sizes gives each chunk
+// its place (lanes >= N hold the end), and each output word finds its chunk by
+// a search over the lanes' places; what is not a header byte is zero. Every
+// cross-lane read happens with all 64 lanes active (the round loops are
+// wave-uniform; only the store is predicated).
+__global__ __launch_bounds__(64 * MUT_WAVES) void k_mutate_packets(u8 *feed, u64 stride, const u32 *lanes,
+                                                                   const u64 *index, const u32 *ncorpus, u32 n,
+                                                                   u64 seed, wtfpkt::Params q, const u8 *arena,
+                                                                   const u64 *arena_off, u64 *feed_pos,
+                                                                   u64 *feed_end) {
+  const u32 i = blockIdx.x * MUT_WAVES + threadIdx.x / 64, l = threadIdx.x & 63;
+  if (i >= n) return;
+  const u32 lane = lanes[i];
+  u8 *dst = feed + (u64)lane * stride;
+  wtfmut::Rng g(seed, index[i]);
+  const u64 s0 = g.s;
+  u32 size;
+  if (g.R(5) == 4) {
+    const u32 N = (u32)g.R(q.GenMaxPackets) + 1;
+    const wtfpkt::GenPacket k = wtfpkt::gen_packet(s0, l, q);
+    const u32 len = l < N ? 4 + k.w[0] : 0;
+    u32 incl = len;  // inclusive prefix over the wave
+    for (u32 d = 1; d < 64; d <<= 1) {
+      const u32 up = __shfl_up(incl, d);
+      if (l >= d) incl += up;
+    }
+    size = __shfl(incl, 63);
+    const u32 at = l < N ? incl - len : ~0u;  // this lane's chunk starts here; no chunk: past every byte
+    for (u32 j0 = 0; j0 < size; j0 += 256) {
+      const u32 j = j0 + 4 * l;
+      u32 c = 0;  // the last chunk that starts at or before byte j (chunk 0 starts at 0)
+      for (u32 d = 32; d; d >>= 1)
+        if (__shfl(at, c + d) <= j) c += d;
+      const u32 c1 = c < 63 ? c + 1 : 63;  // a word meets at most one boundary: chunks have 12 bytes or more
+      const u32 at0 = __shfl(at, c), at1 = __shfl(at, c1);
+      const u32 a0 = __shfl(k.w[0], c), a1 = __shfl(k.w[1], c), a2 = __shfl(k.w[2], c);
+      const u32 b0 = __shfl(k.w[0], c1), b1 = __shfl(k.w[1], c1), b2 = __shfl(k.w[2], c1);
+      u32 w = 0;
+      for (u32 b = 0; b < 4; b++) {
+        const u32 pos = j + b;
+        if (pos >= size) break;
+        const bool nx = c1 != c && pos >= at1;
+        const u32 r = pos - (nx ? at1 : at0);
+        if (r < 12) {
+          const u32 h = r < 4 ? (nx ? b0 : a0) : r < 8 ? (nx ? b1 : a1) : (nx ? b2 : a2);
+          w |= ((h >> (8 * (r & 3))) & 0xff) << (8 * b);
+        }
+      }
+      if (j < size) *(u32 *)(dst + j) = w;
+    }
+  } else {
+    wtfpkt::Plan p;
+    wtfpkt::make_plan(p, g, wtfmut::Corpus{arena, arena_off}, ncorpus[i], q);
+    size = p.size;
+    for (u32 j = 4 * l; j < size; j += 256) {
+      u32 w = 0;
+      for (u32 k = 0; k < 4; k++)
+        if (j + k < size) w |= (u32)wtfpkt::plan_byte(p, j + k) << (8 * k);
+      *(u32 *)(dst + j) = w;
+    }
+  }
+  if (l == 0) {
+    feed_pos[lane] = (u64)lane * stride;
+    feed_end[lane] = (u64)lane * stride + size;
+  }
+}
+
+// wtfgpu_read_whole_feed_lanes: each listed lane's whole feed, from its
+// region's first byte to feed_end (which nothing moves after the feed is
+// written: k_run and k_insert advance feed_pos only), cut to `room` bytes, one
+// block a lane. len ~0u: the lane has no feed.
+__global__ void k_feed_gather_whole(const u8 *feed, u64 stride, const u32 *lanes, u32 n, const u64 *feed_pos,
+                                    const u64 *feed_end, u32 *lens, u8 *out, u64 room) {
+  const u32 i = blockIdx.x;
+  if (i >= n) return;
+  const u32 lane = lanes[i];
+  const bool has = feed_pos[lane] != ~0ull;
+  const u8 *src = feed + (u64)lane * stride;
+  u64 len = has ? feed_end[lane] - (u64)lane * stride : 0;
+  if (len > stride) len = stride;
+  if (threadIdx.x == 0) lens[i] = has ? (u32)len : ~0u;
+  if (len > room) len = room;
+  for (u64 k = threadIdx.x; k < len; k += blockDim.x) out[(u64)i * room + k] = src[k];
 }
 
 __global__ void k_cov_commit(Dev P, const u64 *rips, u64 n) {

@@ -149,6 +149,46 @@ class Engine:
                                            stride), "read_feed_lanes")
         return [None if n == 0xffffffff else out[i, :min(int(n), stride)].tobytes() for i, n in enumerate(lens)]
 
+    # ---- the device packet mutator (csrc/engine_mutate_packets.h)
+    def corpus_add_feed_rc(self, feed: bytes):
+        """(return code, index) of wtfgpu_corpus_add_feed."""
+        idx = C.c_uint32(0xffffffff)
+        rc = self.L.wtfgpu_corpus_add_feed(self.ctx, bytes(feed), len(feed), C.byref(idx))
+        return rc, idx.value
+
+    def corpus_add_feed(self, feed: bytes) -> int:
+        """Index of the new entry; raises DeviceCorpusFull when it does not fit."""
+        rc, idx = self.corpus_add_feed_rc(feed)
+        if rc == abi.ERR_FULL:
+            raise DeviceCorpusFull(f"corpus_add_feed: no room for {len(feed)} bytes")
+        _chk(rc, "corpus_add_feed")
+        return idx
+
+    def mutate_packets_lanes_rc(self, lanes, seed, indices, ncorpus, params) -> int:
+        """wtfgpu_mutate_packets_lanes' return code (asynchronous on the queue);
+        params: the five wtfgpu_packet_params_t values, in order."""
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        ix = np.ascontiguousarray(indices, dtype=np.uint64)
+        nc = np.ascontiguousarray(ncorpus, dtype=np.uint32)
+        assert len(ix) == len(la) and len(nc) == len(la)
+        pp = abi.PacketParams(*params)
+        return self.L.wtfgpu_mutate_packets_lanes(self.ctx, la.ctypes.data_as(C.POINTER(C.c_uint32)), len(la), seed,
+                                                  ix.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  nc.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(pp))
+
+    def mutate_packets_lanes(self, lanes, seed, indices, ncorpus, params):
+        _chk(self.mutate_packets_lanes_rc(lanes, seed, indices, ncorpus, params), "mutate_packets_lanes")
+
+    def read_whole_feed_lanes(self, lanes, stride=abi.FEED_STRIDE):
+        """Each listed lane's whole feed (None: the lane has no feed)."""
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        lens = np.zeros(len(la), dtype=np.uint32)
+        out = np.zeros((len(la), stride), dtype=np.uint8)
+        _chk(self.L.wtfgpu_read_whole_feed_lanes(self.ctx, la.ctypes.data_as(C.POINTER(C.c_uint32)), len(la),
+                                                 lens.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 out.ctypes.data_as(C.c_void_p), stride), "read_whole_feed_lanes")
+        return [None if n == 0xffffffff else out[i, :min(int(n), stride)].tobytes() for i, n in enumerate(lens)]
+
     # ---- registers
     def read_gprs(self, first=0, count=None) -> np.ndarray:
         count = self.nlanes - first if count is None else count

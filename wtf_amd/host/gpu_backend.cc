@@ -293,6 +293,21 @@ bool GpuBackend_t::DeviceCorpusAdd(const uint8_t *P, size_t N) {
   return mut_on_ && wtfgpu_corpus_add(ctx_, P, N, nullptr) == WTFGPU_OK;
 }
 
+// --device-packets: needs the Feed action on the device: nothing else hands a
+// lane the packets of an ordered testcase.
+bool GpuBackend_t::SetDevicePackets(uint64_t Seed, const PacketMutator_t &M, uint64_t MaxEntries, uint64_t MaxBytes) {
+  if (!feed_action_ || mut_on_ || !M.FeedToTestcase) return false;
+  if (wtfgpu_corpus_alloc(ctx_, MaxEntries, MaxBytes) != WTFGPU_OK) return false;
+  pkt_on_ = true;
+  pkt_ = M;
+  mut_seed_ = Seed;
+  return true;
+}
+
+bool GpuBackend_t::DeviceCorpusAddFeed(const uint8_t *P, size_t N) {
+  return pkt_on_ && wtfgpu_corpus_add_feed(ctx_, P, N, nullptr) == WTFGPU_OK;
+}
+
 // The testcase as the feed's one chunk (u32 size, bytes); the device applies
 // the declared insert to it before the lane runs.
 bool GpuBackend_t::SetInsert(const uint8_t *Data, const uint64_t Size) {
@@ -1786,7 +1801,7 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
     mut_lanes_.clear();
     mut_idx_.clear();
     mut_nc_.clear();
-    if (mut_on_)
+    if (mut_on_ || pkt_on_)
       for (size_t i = 0; i < n; i++)
         if (In[i].ordered) {
           mut_lanes_.push_back(fresh[i]);
@@ -1841,9 +1856,16 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
     }
     if (!mut_lanes_.empty()) {
       const auto tmu = Clock::now();
-      if (wtfgpu_mutate_feed_lanes(ctx_, mut_lanes_.data(), (uint32_t)mut_lanes_.size(), mut_seed_, mut_idx_.data(),
-                                   mut_nc_.data(), mut_max_len_) != WTFGPU_OK)
+      if (pkt_on_) {
+        const wtfgpu_packet_params_t pp{pkt_.GenMaxPackets, pkt_.GenCommands, pkt_.GenMaxBody, pkt_.FlipOneIn,
+                                        pkt_.InsertMaxPackets};
+        if (wtfgpu_mutate_packets_lanes(ctx_, mut_lanes_.data(), (uint32_t)mut_lanes_.size(), mut_seed_,
+                                        mut_idx_.data(), mut_nc_.data(), &pp) != WTFGPU_OK)
+          return false;
+      } else if (wtfgpu_mutate_feed_lanes(ctx_, mut_lanes_.data(), (uint32_t)mut_lanes_.size(), mut_seed_,
+                                          mut_idx_.data(), mut_nc_.data(), mut_max_len_) != WTFGPU_OK) {
         return false;
+      }
       stats_.mutate_dev_ms += ms_since(tmu);
     }
     // lanes InsertTestcase stopped never run: marked STOPPED on the device, so
@@ -2142,6 +2164,24 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
         if (P.rb_lens[k] > mut_max_len_) return false;  // no feed (~0u), or not the mutator's chunk
       stats_.readback_tcs += m;
     }
+  } else if (pkt_on_) {  // --device-packets: the whole feeds, each turned into the testcase the target keeps
+    for (uint32_t l : finished)
+      if (ordered_[l] && !plain_[l]) P.rb_lanes.push_back(l);
+    if (!P.rb_lanes.empty()) {
+      const size_t m = P.rb_lanes.size();
+      const uint64_t stride = kFeedRegion;
+      P.rb_lens.resize(m);
+      if (P.rb_bytes.size() < m * stride) P.rb_bytes.resize(m * stride);
+      if (wtfgpu_read_whole_feed_lanes(ctx_, P.rb_lanes.data(), (uint32_t)m, P.rb_lens.data(), P.rb_bytes.data(),
+                                       stride) != WTFGPU_OK)
+        return false;
+      P.rb_tcs.resize(m);
+      for (size_t k = 0; k < m; k++) {
+        if (P.rb_lens[k] > stride) return false;  // no feed (~0u)
+        P.rb_tcs[k] = pkt_.FeedToTestcase(P.rb_bytes.data() + k * stride, P.rb_lens[k]);
+      }
+      stats_.readback_tcs += m;
+    }
   }
   const size_t base = Out.size();
   Out.resize(base + finished.size());
@@ -2152,10 +2192,15 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
       Out[base + i] = StreamResult_t{tag_[l], nullptr, ex[l - first].icount};
     } else {
       Out[base + i] = StreamResult_t{tag_[l], &lres_[l]};
-      if (mut_on_ && ordered_[l]) {  // its place in the read-back list (ascending, as finished is)
+      if ((mut_on_ || pkt_on_) && ordered_[l]) {  // its place in the read-back list (ascending, as finished is)
         const size_t k = (size_t)(std::lower_bound(P.rb_lanes.begin(), P.rb_lanes.end(), l) - P.rb_lanes.begin());
-        Out[base + i].tc = P.rb_bytes.data() + k * std::max<uint32_t>(mut_max_len_, 1);
-        Out[base + i].tc_size = P.rb_lens[k];
+        if (pkt_on_) {
+          Out[base + i].tc = (const uint8_t *)P.rb_tcs[k].data();
+          Out[base + i].tc_size = P.rb_tcs[k].size();
+        } else {
+          Out[base + i].tc = P.rb_bytes.data() + k * std::max<uint32_t>(mut_max_len_, 1);
+          Out[base + i].tc_size = P.rb_lens[k];
+        }
       }
     }
     busy_[l] = 0;  // not runnable until refilled (a finished lane keeps its exit status)

@@ -112,9 +112,14 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   // the refill, and the harvest reads back (wtfgpu_read_feed_lanes) the ones
   // whose result is not the common counted one
   bool HasDeviceMutator() const override { return true; }
-  bool MutatesOnDevice() const override { return mut_on_; }
+  bool MutatesOnDevice() const override { return mut_on_ || pkt_on_; }
   bool SetDeviceMutate(uint64_t Seed, uint32_t MaxLen, uint64_t MaxEntries, uint64_t MaxBytes) override;
   bool DeviceCorpusAdd(const uint8_t *P, size_t N) override;
+  // --device-packets: the same with wtfgpu_mutate_packets_lanes and
+  // wtfgpu_read_whole_feed_lanes; a feed read back becomes the testcase
+  // (PacketMutator_t::FeedToTestcase) before the session sees it
+  bool SetDevicePackets(uint64_t Seed, const PacketMutator_t &M, uint64_t MaxEntries, uint64_t MaxBytes) override;
+  bool DeviceCorpusAddFeed(const uint8_t *P, size_t N) override;
   uint32_t FreeLanes() const override;
   bool StreamStep(const Target_t &Target, const std::vector<StreamTestcase_t> &In, uint64_t Slice,
                   std::vector<StreamResult_t> &Out, ModuleSlots *Slots, size_t *Taken) override;
@@ -316,6 +321,7 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
     // at a stride of mut_max_len_), valid until the part's next harvest
     std::vector<uint32_t> rb_lanes, rb_lens;
     std::vector<uint8_t> rb_bytes;
+    std::vector<std::string> rb_tcs;  // --device-packets: the testcases made of the feeds read back
     // the slice's read-back queued behind it (wtfgpu_prefetch_results /
     // _coverage), pinned: byte and dirty-page counts, StopWithArgs
     // arguments, the coverage entry count
@@ -368,6 +374,9 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   std::vector<uint8_t> ordered_;
   std::vector<uint32_t> mut_lanes_, mut_nc_;
   std::vector<uint64_t> mut_idx_;
+  // --device-packets: on, and the target's declaration (the stream's params, FeedToTestcase)
+  bool pkt_on_ = false;
+  PacketMutator_t pkt_{};
   bool insert_action_ = false;                   // the declared insert is on the device (wtfgpu_set_insert)
   int upload_feed(uint32_t n);                   // lanes [0, n)
   std::unordered_set<uint64_t> aggregate_;

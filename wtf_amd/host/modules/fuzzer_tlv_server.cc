@@ -705,6 +705,49 @@ class CustomMutator_t : public Mutator_t {
   }
 };
 
-Target_t TlvServer("tlv_server", Init, InsertTestcase, Restore, CustomMutator_t::Create, PrepareInsert);
+// The canonical JSON Serialize writes, straight from a feed's chunks (the
+// feed the device packet mutator made and the gpu backend read back): the
+// testcase the session keeps. The feed is valid (its chunks tile it).
+std::string FeedToTestcase(const uint8_t *Feed, const size_t FeedSize) {
+  std::string S(16 + 6 * FeedSize, '\0');  // a chunk's 12 bytes take at most 72 characters, a body byte 4
+  char *o = S.data();
+  o = PutLit(o, "{\"Packets\":[", 12);
+  for (size_t At = 0; At + 12 <= FeedSize;) {
+    uint32_t Size, Command;
+    uint16_t Id, BodySize;
+    memcpy(&Size, Feed + At, 4);
+    memcpy(&Command, Feed + At + 4, 4);
+    memcpy(&Id, Feed + At + 8, 2);
+    memcpy(&BodySize, Feed + At + 10, 2);
+    if (Size < 8 || Size > FeedSize - At - 4) break;
+    if (At) *o++ = ',';
+    o = PutLit(o, "{\"Body\":[", 9);
+    const uint8_t *Body = Feed + At + 12;
+    for (uint32_t j = 0; j + 8 < Size; j++) {
+      if (j) *o++ = ',';
+      memcpy(o, kDigits.s[Body[j]], 4);
+      o += kDigits.n[Body[j]];
+    }
+    o = PutLit(o, "],\"BodySize\":", 13);
+    o = PutU64(o, BodySize);
+    o = PutLit(o, ",\"Command\":", 11);
+    o = PutU64(o, Command);
+    o = PutLit(o, ",\"Id\":", 6);
+    o = PutU64(o, Id);
+    *o++ = '}';
+    At += 4 + (size_t)Size;
+  }
+  o = PutLit(o, "]}", 2);
+  S.resize((size_t)(o - S.data()));
+  return S;
+}
+
+// --device-packets: CustomMutator_t's constants (above) as the params of the
+// device packet mutator's stream
+const PacketMutator_t PacketMutator{/*GenMaxPackets=*/10, /*GenCommands=*/11, /*GenMaxBody=*/100, /*FlipOneIn=*/3,
+                                    /*InsertMaxPackets=*/10, FeedToTestcase, TestcaseFeedBytes};
+
+Target_t TlvServer("tlv_server", Init, InsertTestcase, Restore, CustomMutator_t::Create, PrepareInsert,
+                   &PacketMutator);
 
 }  // namespace TlvServer

@@ -260,6 +260,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     else if (a == "--edges") O.edges = true;
     else if (a == "--device-attrib") O.device_attrib = true;
     else if (a == "--device-mutate") O.device_mutate = true;
+    else if (a == "--device-packets") O.device_packets = true;
     else if (a == "--trace-path") O.trace_path = next("--trace-path");
     else if (a == "--trace-type") O.trace_type = next("--trace-type");
     else if (a == "--trace-cap") O.trace_cap = (uint32_t)strtoul(next("--trace-cap"), nullptr, 0);
@@ -288,6 +289,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
   }
   if (const char *e = getenv("WTF_RCCL_FORCE")) O.rccl_force = O.rccl_force || atoi(e) != 0;
   if (const char *e = getenv("WTFGPU_DEVICE_MUTATE")) O.device_mutate = O.device_mutate || atoi(e) != 0;
+  if (const char *e = getenv("WTFGPU_DEVICE_PACKETS")) O.device_packets = O.device_packets || atoi(e) != 0;
   if (O.world < 1 || O.rank < 0 || O.rank >= O.world) {
     fprintf(stderr, "--rank must be in [0, --world)\n");
     return false;
@@ -302,11 +304,24 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
                     "--module-so\n");
     return false;
   }
+  if (O.device_packets && O.mode != "run") {
+    if (O.device_mutate) {
+      fprintf(stderr, "--device-packets cannot be combined with the byte-buffer device mutator: a session has one "
+                      "device stream\n");
+      return false;
+    }
+    if (O.mode == "master" || !O.address.empty() || O.world > 1 || !O.module_so.empty()) {
+      fprintf(stderr, "--device-packets is for one in-process fuzz session: not with master, --address, --world > 1 "
+                      "or --module-so\n");
+      return false;
+    }
+  }
   if (O.name.empty() || O.target.empty()) {
     fprintf(stderr, "usage: [run|fuzz|master] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
                     "       [--lanes n] [--overlay-pages k] [--spill-pages s [--spill-lane-max x]] [--runs n] [--seconds s] [--seed s] [--full-coverage]\n"
                     "       [--serial-mutation] [--slice-steps s] [--regroup-steps r] [--rank r --world n [--exchange host:port | --nccl-id-file f]]\n"
                     "       [--address tcp://ip:port|unix://path [--batched] [--nodes k]] [--edges] [--device-attrib] [--device-mutate]\n"
+                    "       [--device-packets]\n"
                     "       [--trace-path dir [--trace-type rip|cov|tenet] [--trace-cap n] [--tenet-cap bytes]] [--module-so m.so] [--serial]\n");
     return false;
   }
@@ -734,7 +749,7 @@ bool FuzzSession::Start() {
   }
   t0_ = Clock::now();
   stream_ = O_.slice && Exec_.CanStream();
-  if (O_.device_mutate && !StartDeviceMutate()) {
+  if ((O_.device_mutate && !StartDeviceMutate()) || (O_.device_packets && !StartDevicePackets())) {
     Refused_ = true;
     return false;
   }
@@ -781,8 +796,46 @@ bool FuzzSession::StartDeviceMutate() {
   return true;
 }
 
+// --device-packets: the same refusals for a target's declared packet mutator.
+bool FuzzSession::StartDevicePackets() {
+  const PacketMutator_t *M = Target_.PacketMutator;
+  if (!M || !M->FeedToTestcase || !M->TestcaseToFeed) {
+    printf("--device-packets: target %s declares no packet mutator (PacketMutator_t)\n", O_.name.c_str());
+    return false;
+  }
+  if (!DevicePacketsParamsValid(*M)) {
+    printf("--device-packets: target %s's packet mutator params are out of range\n", O_.name.c_str());
+    return false;
+  }
+  if (Exec_.HasDeviceMutator()) {  // it mutates on its device, in streaming runs
+    if (!stream_) {
+      printf("--device-packets needs a streaming run on this executor (--slice-steps != 0)\n");
+      return false;
+    }
+    if (!Exec_.SetDevicePackets(O_.seed, *M, DevCorpus_.MaxEntries, DevCorpus_.MaxBytes)) {
+      printf("--device-packets: the executor does not serve target %s's packets from a feed on the device\n",
+             O_.name.c_str());
+      return false;
+    }
+  }
+  DevOnDevice_ = Exec_.MutatesOnDevice();
+  return true;
+}
+
 // A corpus entry the session keeps, for the device mutator too (in account order)
 void FuzzSession::DevCorpusAdd(const uint8_t *Tc, size_t Size) {
+  if (O_.device_packets) {  // as the feed the lanes consume
+    std::vector<uint8_t> Feed;
+    if (!Target_.PacketMutator->TestcaseToFeed(Tc, Size, Feed) || !DevCorpus_.AddFeed(Feed.data(), Feed.size())) {
+      DevDropped_++;
+      return;
+    }
+    if (DevOnDevice_ && !Exec_.DeviceCorpusAddFeed(Feed.data(), Feed.size())) {
+      printf("--device-packets: the device corpus refused an entry the host copy took\n");
+      exit(1);
+    }
+    return;
+  }
   if (!O_.device_mutate) return;
   if (!DevCorpus_.Add(Tc, Size)) {
     DevDropped_++;
@@ -843,7 +896,7 @@ TcBatch FuzzSession::MakeBatch(uint64_t n) {
   // a read-only view of the corpus (deterministic for a seed whatever the
   // thread count; the corpus does not change while the batch is built)
   const size_t Need = n - Made;
-  if (O_.device_mutate && DevCorpus_.Count()) {
+  if (DevStream() && DevCorpus_.Count()) {
     // the device mutator's stream: testcase NextIndex_ over the corpus as it
     // stands; as an order for an executor that mutates on the device, else
     // made here from the same definition. Neither the mutation workers nor
@@ -851,11 +904,16 @@ TcBatch FuzzSession::MakeBatch(uint64_t n) {
     const uint32_t NC = (uint32_t)DevCorpus_.Count();
     Batch.push_back(NewArena());
     TcArena &A = *Batch.back();
-    std::vector<uint8_t> Buf(std::max<uint32_t>(DevMaxLen_, 1));
+    std::vector<uint8_t> Buf(O_.device_packets ? kDevicePacketsMaxFeed : std::max<uint32_t>(DevMaxLen_, 1));
     for (; Made < n; Made++) {
       const uint64_t Index = NextIndex_++;
       if (DevOnDevice_) {
         A.AddOrder(Index, NC);
+      } else if (O_.device_packets) {  // the feed, then the testcase the target makes of it
+        const PacketMutator_t &M = *Target_.PacketMutator;
+        const std::string Tc = M.FeedToTestcase(Buf.data(), DevicePackets(O_.seed, Index, DevCorpus_, NC, M, Buf.data()));
+        A.Add(Tc.data(), Tc.size());
+        if (Prepare_) A.Prepare(Prepare_, PrepScratch_);
       } else {
         A.Add(Buf.data(), DeviceMutate(O_.seed, Index, DevCorpus_, NC, DevMaxLen_, Buf.data()));
         if (Prepare_) A.Prepare(Prepare_, PrepScratch_);
@@ -1336,7 +1394,7 @@ std::string FuzzSession::SummaryJson() const {
            "\"merges\":%llu,\"merged_map_bytes\":%llu,"
            "\"merge_ms\":%.3f,\"produce_wait_ms\":%.3f,\"account_ms\":%.3f,\"make_ms\":%.3f,\"step_ms\":%.3f,\"fill_ms\":%.3f,"
            "\"newcov_ms\":%.3f,\"crashsave_ms\":%.3f,\"call_ms\":%.3f,\"cpu_s\":%.3f,\"mutate_cpu_ms\":%.3f,"
-           "\"device_mutate\":%d,\"device_corpus_dropped\":%llu,"
+           "\"device_mutate\":%d,\"device_packets\":%d,\"device_corpus_dropped\":%llu,"
            "\"backend\":",
            O_.name.c_str(), Exec_.Lanes(), X_ ? X_->Rank() : 0, X_ ? X_->World() : 1,
            (unsigned long long)S_.batches, (unsigned long long)S_.execs, (unsigned long long)S_.retired, Wall,
@@ -1346,7 +1404,8 @@ std::string FuzzSession::SummaryJson() const {
            (unsigned long long)S_.error_retired, (unsigned long long)S_.merged_rips,
            (unsigned long long)S_.merges, (unsigned long long)S_.merged_map_bytes, S_.merge_ms, S_.produce_wait_ms,
            S_.account_ms, S_.make_ms, S_.step_ms, S_.fill_ms, S_.newcov_ms, S_.crashsave_ms, S_.call_ms, ProcessCpuSeconds(),
-           MutateCpuNs_.load() * 1e-6, O_.device_mutate ? 1 : 0, (unsigned long long)DevDropped_);
+           MutateCpuNs_.load() * 1e-6, O_.device_mutate ? 1 : 0, O_.device_packets ? 1 : 0,
+           (unsigned long long)DevDropped_);
   return std::string(b) + Exec_.StatsJson() + "}";
 }
 

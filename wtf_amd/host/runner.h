@@ -98,6 +98,16 @@ class Executor_t {
     return false;
   }
   virtual bool DeviceCorpusAdd(const uint8_t *, size_t) { return false; }
+  // --device-packets: the same for a target's declared packet mutator
+  // (PacketMutator_t; csrc/engine_mutate_packets.h). Orders are made by the
+  // executor into the lanes' feeds; the corpus entries it is given are feeds,
+  // and StreamResult_t::tc is what PacketMutator_t::FeedToTestcase gives for
+  // the feed it read back. Default: it cannot.
+  virtual bool SetDevicePackets(uint64_t /*Seed*/, const PacketMutator_t & /*M*/, uint64_t /*MaxEntries*/,
+                                uint64_t /*MaxBytes*/) {
+    return false;
+  }
+  virtual bool DeviceCorpusAddFeed(const uint8_t *, size_t) { return false; }
   virtual uint32_t FreeLanes() const { return 0; }
   virtual bool StreamStep(const Target_t &, const std::vector<StreamTestcase_t> &, uint64_t,
                           std::vector<StreamResult_t> &, ModuleSlots *, size_t *Taken) {
@@ -234,6 +244,10 @@ struct RunnerOptions {
   // --device-mutate (also WTFGPU_DEVICE_MUTATE=1): the device mutator's stream
   // (csrc/engine_mutate.h) instead of the target's host mutator
   bool device_mutate = false;
+  // --device-packets (also WTFGPU_DEVICE_PACKETS=1): the device packet
+  // mutator's stream (csrc/engine_mutate_packets.h) instead of the host
+  // mutator of a target that declares a PacketMutator_t
+  bool device_packets = false;
   std::string trace_path;    // run: --trace-path dir (one <input>.trace per input, subcommands.cc:52-74)
   std::string trace_type = "rip";  // run: --trace-type rip | cov | tenet (wtf.cc:197-200)
   uint32_t trace_cap = 1u << 20;   // run: rips kept per testcase
@@ -345,11 +359,21 @@ struct DeviceCorpus {
   uint64_t MaxEntries = 1u << 16, MaxBytes = 64ull << 20;
   size_t Count() const { return Off.size() - 1; }
   bool Add(const uint8_t *P, size_t N);
+  // --device-packets: a feed, as the entry wtfgpu_corpus_add_feed makes of it
+  // (csrc/engine_mutate_packets.h); refuses what that call refuses
+  bool AddFeed(const uint8_t *Feed, size_t N);
 };
 // testcase `Index` of the stream `Seed` over the first NCorpus entries, into Out (MaxLen bytes of room); its size
 size_t DeviceMutate(uint64_t Seed, uint64_t Index, const DeviceCorpus &C, uint32_t NCorpus, uint32_t MaxLen,
                     uint8_t *Out);
 constexpr uint32_t kDeviceMutateMaxLen = 16380;  // WTFGPU_FEED_STRIDE - 4
+// --device-packets: testcase `Index` of the packet stream `Seed` over the first
+// NCorpus entries (feeds, AddFeed), as a feed into Out (kDevicePacketsMaxFeed
+// bytes of room); its size
+size_t DevicePackets(uint64_t Seed, uint64_t Index, const DeviceCorpus &C, uint32_t NCorpus, const PacketMutator_t &M,
+                     uint8_t *Out);
+bool DevicePacketsParamsValid(const PacketMutator_t &M);
+constexpr uint32_t kDevicePacketsMaxFeed = 16384;  // WTFGPU_FEED_STRIDE
 
 // The fuzz loop of one node / shard, one batch per Step(): an in-process
 // master (corpus, mutator, crash saving: server.h:629-886) feeding the
@@ -441,6 +465,8 @@ class FuzzSession {
   bool DevOnDevice_ = false;  // the executor mutates (orders); else the session materialises
   std::vector<uint8_t> PrepScratch_;  // PrepareInsert's scratch for materialised testcases
   bool StartDeviceMutate();   // the refusals; false = a message was printed
+  bool StartDevicePackets();  // --device-packets: the same
+  bool DevStream() const { return O_.device_mutate || O_.device_packets; }  // testcases come from a device stream
   void DevCorpusAdd(const uint8_t *Tc, size_t Size);
   std::string LastNewCov_;  // the testcase last passed to Mutator_->OnNewCoverage
   bool HaveNewCov_ = false;

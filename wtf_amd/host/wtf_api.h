@@ -543,6 +543,19 @@ enum class PreparedInsert_t : int8_t {
 };
 using PrepareInsert_t = PreparedInsert_t (*)(const uint8_t *, size_t, std::vector<uint8_t> &Out);
 
+// A packet-list mutator declared as data (this repository's extension):
+// --device-packets makes such a target's testcases from the lanes' feed form
+// with the stream of csrc/engine_mutate_packets.h, on the device where the
+// executor can. The five values are that stream's params; the two functions
+// convert between a feed (per packet: u32 Size, u32 Command, u16 Id, u16
+// BodySize, Body) and the testcase the session keeps.
+// TestcaseToFeed(FeedToTestcase(f)) == f for every valid feed.
+struct PacketMutator_t {
+  uint32_t GenMaxPackets, GenCommands, GenMaxBody, FlipOneIn, InsertMaxPackets;
+  std::string (*FeedToTestcase)(const uint8_t *Feed, size_t FeedSize);
+  bool (*TestcaseToFeed)(const uint8_t *Testcase, size_t TestcaseSize, std::vector<uint8_t> &Feed);
+};
+
 struct Target_t {
   using Init_t = bool (*)(const Options_t &, const CpuState_t &);
   using InsertTestcase_t = bool (*)(const uint8_t *, const size_t);
@@ -552,7 +565,7 @@ struct Target_t {
   explicit Target_t(const std::string &Name, const Init_t Init, const InsertTestcase_t InsertTestcase,
                     const Restore_t Restore = []() { return true; },
                     const CreateMutator_t CreateMutator = LibfuzzerMutator_t::Create,
-                    const PrepareInsert_t PrepareInsert = nullptr);
+                    const PrepareInsert_t PrepareInsert = nullptr, const PacketMutator_t *PacketMutator = nullptr);
 
   std::string Name;
   Init_t Init = nullptr;
@@ -560,6 +573,7 @@ struct Target_t {
   Restore_t Restore = nullptr;
   CreateMutator_t CreateMutator = nullptr;
   PrepareInsert_t PrepareInsert = nullptr;  // optional (above)
+  const PacketMutator_t *PacketMutator = nullptr;  // optional: --device-packets
 };
 
 struct Targets_t {

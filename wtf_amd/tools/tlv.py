@@ -84,14 +84,13 @@ def _elf(path: str):
     return segs, syms
 
 
-def build(state_dir: str, work_dir: str | None = None, packet: str = "rw") -> dict:
-    """Compiles the guest and writes mem.dmp / regs.json / symbol-store.json
-    into state_dir. Returns the guest symbol table. `packet` maps the packet
+def space(work_dir: str, packet: str = "rw"):
+    """Compiles the guest: (AddressSpace, CPU state, wtf symbol store, guest
+    symbol table) of the snapshot build() writes. `packet` maps the packet
     buffer page read-write ("rw", the real server), read-only ("ro": the
     module's writes still land, Backend_t::VirtWrite translates without a
     permission check, backend.cc:91-121) or not at all ("none": the module's
     write fails and its handler aborts)."""
-    work_dir = work_dir or state_dir
     os.makedirs(work_dir, exist_ok=True)
     elf = os.path.join(work_dir, "tlv_server_guest.elf")
     compile_guest(elf)
@@ -141,6 +140,13 @@ def build(state_dir: str, work_dir: str | None = None, packet: str = "rw") -> di
         "nt!KiRaiseSecurityCheckFailure": KI_RAISE,
         "verifier": 0,
     }
+    return sp, st, symbols, syms
+
+
+def build(state_dir: str, work_dir: str | None = None, packet: str = "rw") -> dict:
+    """Writes space()'s snapshot as mem.dmp / regs.json / symbol-store.json
+    into state_dir. Returns the guest symbol table."""
+    sp, st, symbols, syms = space(work_dir or state_dir, packet)
     write_snapshot(state_dir, sp, st, symbols)
     return syms
 
