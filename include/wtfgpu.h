@@ -419,6 +419,21 @@ int wtfgpu_mutate_packets_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t
  * lane consumes it, until the lane's next feed). */
 int wtfgpu_read_whole_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t *lens, uint8_t *bytes,
                                  uint64_t stride);
+/* The listed lanes' feeds, packed: only the bytes that exist travel, into a
+ * pinned host buffer the engine owns. whole = 0 reads what
+ * wtfgpu_read_feed_lanes reads (the first chunk without its size, the same
+ * clamp), whole = 1 what wtfgpu_read_whole_feed_lanes reads; lens[i] is as in
+ * those calls (~0u: the lane has no feed, and it takes no room). offs[i] is
+ * where lane lanes[i]'s bytes start in *bytes: the sum, in list order and in 64
+ * bits, of the earlier lengths each rounded up to 16. *total is the whole sum,
+ * and the padding bytes are zero. A lane listed twice gets two copies. *bytes
+ * stays valid until the next packed read on the same queue (one on the other
+ * queue does not disturb it) or wtfgpu_destroy; with *total == 0 it may be
+ * anything. n == 0 gives *total = 0. Waits for the current queue.
+ * WTFGPU_ERR_INVALID, before anything is queued, for a lane outside the
+ * context, a null pointer, or a `whole` above 1. */
+int wtfgpu_read_feeds_packed(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t whole, uint32_t *lens,
+                             uint64_t *offs, const uint8_t **bytes, uint64_t *total);
 /* New-coverage sets of a lane list (as wtfgpu_read_coverage); a call whose
  * cap covers the count also empties those lanes' sets (cap = 0 with an empty
  * result included). */

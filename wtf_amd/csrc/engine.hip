@@ -66,6 +66,10 @@ struct QueueRes {
   u8 *d_pcov = nullptr;
   hipEvent_t ev_pre = nullptr;
   bool pre_valid = false;
+  // wtfgpu_read_feeds_packed: the pinned bytes k_feed_pack writes and the
+  // caller reads until the queue's next packed read
+  u8 *h_pack = nullptr;
+  u64 h_pack_cap = 0;
 };
 
 struct wtfgpu_ctx {
@@ -260,6 +264,8 @@ void queue_destroy(QueueRes &q) {
   dfree(q.d_scratch);
   dfree(q.d_exq);
   dfree(q.d_pcov);
+  if (q.h_pack) (void)hipHostFree(q.h_pack);
+  q.h_pack = nullptr;
   if (q.h_stage) (void)hipHostFree(q.h_stage);
   q.h_stage = nullptr;
   if (q.h_ring) (void)hipHostFree(q.h_ring);
@@ -1255,6 +1261,66 @@ int wtfgpu_read_whole_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t 
   HIPCHK(hipMemcpyAsync(lens, S + s[0].off, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
   if (stride) return read_back(c, bytes, s[1]);
   HIPCHK(hipStreamSynchronize(c->q->stream));
+  return WTFGPU_OK;
+}
+
+// The packed read-back (engine_feedpack.h): lengths, a 64-bit scan and the
+// first wait give the caller lens, offs and the total; then k_feed_pack writes
+// exactly `total` bytes into the queue's pinned buffer, grown to the total
+// (known only now, and not n x stride), and the second wait returns them.
+int wtfgpu_read_feeds_packed(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32_t whole, uint32_t *lens,
+                             uint64_t *offs, const uint8_t **bytes, uint64_t *total) {
+  if (!c || !c->d_gpr || !bytes || !total || (n && (!lanes || !lens || !offs)) || whole > 1 ||
+      !lane_list_in_range(c, lanes, n))
+    return WTFGPU_ERR_INVALID;
+  *total = 0;
+  *bytes = c->q->h_pack;
+  if (n == 0) return WTFGPU_OK;
+  if (!c->d_feedpos || c->feed_stride == 0) {  // no per-lane regions yet: no lane has a feed in one
+    for (u32 i = 0; i < n; i++) {
+      lens[i] = ~0u;
+      offs[i] = 0;
+    }
+    return WTFGPU_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  QueueRes &q = *c->q;
+  size_t tmp_n = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_n, (u64 *)nullptr, (u64 *)nullptr, (int)(n + 1), q.stream));
+  Side s[] = {side_room((u64)n * 4), side_room((u64)(n + 1) * 8), side_room((u64)(n + 1) * 8), side_room(tmp_n)};
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, s, 4)) return rc;
+  u8 *const S = q.d_scratch;
+  u32 *const d_lens = (u32 *)(S + s[0].off);
+  u64 *const d_pad = (u64 *)(S + s[1].off), *const d_offs = (u64 *)(S + s[2].off);
+  k_feed_lens<<<n / 256 + 1, 256, 0, q.stream>>>(c->d_feeddata, c->feed_stride, (const u32 *)S, n, c->d_feedpos,
+                                                 c->d_feedend, whole, d_lens, d_pad);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(S + s[3].off, tmp_n, d_pad, d_offs, (int)(n + 1), q.stream));
+  u64 sum = 0;
+  HIPCHK(hipMemcpyAsync(lens, d_lens, (u64)n * 4, hipMemcpyDeviceToHost, q.stream));
+  HIPCHK(hipMemcpyAsync(offs, d_offs, (u64)n * 8, hipMemcpyDeviceToHost, q.stream));
+  HIPCHK(hipMemcpyAsync(&sum, d_offs + n, 8, hipMemcpyDeviceToHost, q.stream));
+  HIPCHK(hipStreamSynchronize(q.stream));
+  if (sum > (u64)n * c->feed_stride) return WTFGPU_ERR_STATE;  // (cannot be: every place is at most a region)
+  if (sum == 0) return WTFGPU_OK;
+  if (q.h_pack_cap < sum) {  // geometric; the bytes of the queue's last packed read end here, as declared
+    const u64 want = std::max<u64>(std::max<u64>(sum, 2 * q.h_pack_cap), 1ull << 20);
+    if (q.h_pack) (void)hipHostFree(q.h_pack);
+    q.h_pack = nullptr;
+    q.h_pack_cap = 0;
+    if (hipHostMalloc((void **)&q.h_pack, want, hipHostMallocDefault) != hipSuccess) return WTFGPU_ERR_OOM;
+    q.h_pack_cap = want;
+  }
+  // k_feed_pack writes the pinned buffer itself: no device staging, no DMA
+  // (measured against staging plus one hipMemcpyAsync: profiles/packed_readback_ab.txt)
+  u8 *d_out = nullptr;
+  HIPCHK(hipHostGetDevicePointer((void **)&d_out, q.h_pack, 0));
+  k_feed_pack<<<(n + MUT_WAVES - 1) / MUT_WAVES, 64 * MUT_WAVES, 0, q.stream>>>(
+      c->d_feeddata, c->feed_stride, (const u32 *)S, n, whole, d_lens, d_offs, d_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(q.stream));
+  *bytes = q.h_pack;
+  *total = sum;
   return WTFGPU_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "engine_run.h"
 #include "engine_mutate.h"
 #include "engine_mutate_packets.h"
+#include "engine_feedpack.h"
 
 namespace {
 
@@ -691,6 +692,65 @@ __global__ void k_feed_gather_whole(const u8 *feed, u64 stride, const u32 *lanes
   if (threadIdx.x == 0) lens[i] = has ? (u32)len : ~0u;
   if (len > room) len = room;
   for (u64 k = threadIdx.x; k < len; k += blockDim.x) out[(u64)i * room + k] = src[k];
+}
+
+// wtfgpu_read_feeds_packed (engine_feedpack.h defines the layout): each listed
+// lane's length, as k_feed_gather (whole == 0) or k_feed_gather_whole gives
+// it, and its padded length for the scan; padded[n] = 0, so that the
+// exclusive sum over n + 1 values ends with the total.
+__global__ void k_feed_lens(const u8 *feed, u64 stride, const u32 *lanes, u32 n, const u64 *feed_pos,
+                            const u64 *feed_end, u32 whole, u32 *lens, u64 *padded) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {
+    padded[n] = 0;
+    return;
+  }
+  const u32 lane = lanes[i];
+  const u64 region = (u64)lane * stride;
+  const bool has = feed_pos[lane] != ~0ull;
+  const u32 len = whole ? wtffeedpack::whole_len(has, has ? feed_end[lane] : 0, region, stride)
+                        : wtffeedpack::chunk_len(has, has ? *(const u32 *)(feed + region) : 0, stride);
+  lens[i] = len;
+  padded[i] = wtffeedpack::pad16(len);
+}
+
+// The copy: one wave per listed lane, MUT_WAVES a block, 16 bytes a thread a
+// round, exactly pad16(lens[i]) bytes at out + offs[i] (lens and offs are what
+// k_feed_lens and the scan left, not read again from the feed: what is
+// written is what was sized). A region is 16 KiB-aligned and a place
+// 16-aligned, so whole feeds move as 16-byte loads and stores; a chunk starts
+// at region + 4, 4-aligned only, and is loaded a word at a time. A word is
+// loaded only if it starts below len, which keeps every load inside the
+// region (len <= stride - skip, a multiple of 4), and the bytes at and after
+// len are masked to zero: the padding. The round loop is wave-uniform.
+__global__ __launch_bounds__(64 * MUT_WAVES) void k_feed_pack(const u8 *feed, u64 stride, const u32 *lanes, u32 n,
+                                                              u32 whole, const u32 *lens, const u64 *offs, u8 *out) {
+  const u32 i = blockIdx.x * MUT_WAVES + threadIdx.x / 64, l = threadIdx.x & 63;
+  if (i >= n) return;
+  const u32 len = lens[i];
+  if (len == wtffeedpack::kNoFeed) return;
+  const u32 padded = (u32)wtffeedpack::pad16(len);
+  const u8 *src = feed + (u64)lanes[i] * stride + (whole ? 0 : 4);
+  u8 *dst = out + offs[i];
+  for (u32 j0 = 0; j0 < padded; j0 += 16 * 64) {
+    const u32 j = j0 + 16 * l;
+    if (j >= padded) continue;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (whole) {
+      v = *(const uint4 *)(src + j);  // j < padded <= stride: inside the region
+    } else {
+      if (j < len) v.x = *(const u32 *)(src + j);
+      if (j + 4 < len) v.y = *(const u32 *)(src + j + 4);
+      if (j + 8 < len) v.z = *(const u32 *)(src + j + 8);
+      if (j + 12 < len) v.w = *(const u32 *)(src + j + 12);
+    }
+    v.x = wtffeedpack::mask_word(v.x, j, len);
+    v.y = wtffeedpack::mask_word(v.y, j + 4, len);
+    v.z = wtffeedpack::mask_word(v.z, j + 8, len);
+    v.w = wtffeedpack::mask_word(v.w, j + 12, len);
+    *(uint4 *)(dst + j) = v;
+  }
 }
 
 __global__ void k_cov_commit(Dev P, const u64 *rips, u64 n) {

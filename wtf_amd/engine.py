@@ -189,6 +189,28 @@ class Engine:
                                                  out.ctypes.data_as(C.c_void_p), stride), "read_whole_feed_lanes")
         return [None if n == 0xffffffff else out[i, :min(int(n), stride)].tobytes() for i, n in enumerate(lens)]
 
+    def read_feeds_packed_raw(self, lanes, whole=True, null_lens=False):
+        """wtfgpu_read_feeds_packed as it answers: (rc, lens, offs, a copy of the
+        pinned buffer's first `total` bytes, total, the buffer's address).
+        `whole` goes through as an integer; null_lens: a null `lens`."""
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        n = len(la)
+        lens = np.zeros(n, dtype=np.uint32)
+        offs = np.zeros(n, dtype=np.uint64)
+        ptr, total = C.c_void_p(), C.c_uint64()
+        rc = self.L.wtfgpu_read_feeds_packed(self.ctx, la.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(whole),
+                                             None if null_lens else lens.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             offs.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ptr), C.byref(total))
+        buf = C.string_at(ptr.value, total.value) if rc == 0 and total.value else b""
+        return rc, lens, offs, buf, total.value, ptr.value
+
+    def read_feeds_packed(self, lanes, whole=True):
+        """Each listed lane's whole feed (whole=False: its first chunk without the
+        size), read back packed; None: the lane has no feed."""
+        rc, lens, offs, buf, _, _ = self.read_feeds_packed_raw(lanes, whole)
+        _chk(rc, "read_feeds_packed")
+        return [None if n == 0xffffffff else buf[int(o):int(o) + int(n)] for n, o in zip(lens, offs)]
+
     # ---- registers
     def read_gprs(self, first=0, count=None) -> np.ndarray:
         count = self.nlanes - first if count is None else count

@@ -2146,41 +2146,40 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
   target_restore(Target, finished, Slots);
   stats_.target_restore_ms += ms_since(tr);
   const auto tout = Clock::now();
-  // --device-mutate: the ordered testcases whose result is not the common
-  // counted one, read back in one call before their lanes are refilled
+  // --device-mutate / --device-packets: the ordered testcases whose result is
+  // not the common counted one and whose bytes the session will look at (its
+  // filter; without one, all of them), read back packed in one call before
+  // their lanes are refilled: whole = 0 the mutator's chunk, whole = 1 the
+  // packet list's whole feed. The bytes stay in the engine's pinned buffer of
+  // this part's queue until the part's next harvest.
   P.rb_lanes.clear();
-  if (mut_on_) {
-    for (uint32_t l : finished)
-      if (ordered_[l] && !plain_[l]) P.rb_lanes.push_back(l);
-    if (!P.rb_lanes.empty()) {
-      const size_t m = P.rb_lanes.size();
-      const uint64_t stride = std::max<uint32_t>(mut_max_len_, 1);
-      P.rb_lens.resize(m);
-      if (P.rb_bytes.size() < m * stride) P.rb_bytes.resize(m * stride);
-      if (wtfgpu_read_feed_lanes(ctx_, P.rb_lanes.data(), (uint32_t)m, P.rb_lens.data(), P.rb_bytes.data(), stride) !=
-          WTFGPU_OK)
-        return false;
-      for (size_t k = 0; k < m; k++)
-        if (P.rb_lens[k] > mut_max_len_) return false;  // no feed (~0u), or not the mutator's chunk
-      stats_.readback_tcs += m;
+  P.rb_bytes = nullptr;
+  if (mut_on_ || pkt_on_) {
+    P.rb_keepf.resize(finished.size());
+    HostPool::Get().For(finished.size(), 2048, [&](size_t i) {
+      const uint32_t l = finished[i];
+      P.rb_keepf[i] = !(ordered_[l] && !plain_[l]) ? 0 : (!rb_keep_ || rb_keep_(lres_[l])) ? 1 : 2;
+    }, finished.size() >= 8192);
+    for (size_t i = 0; i < finished.size(); i++) {
+      if (P.rb_keepf[i] == 1) P.rb_lanes.push_back(finished[i]);
+      stats_.readback_skipped += P.rb_keepf[i] == 2;
     }
-  } else if (pkt_on_) {  // --device-packets: the whole feeds, each turned into the testcase the target keeps
-    for (uint32_t l : finished)
-      if (ordered_[l] && !plain_[l]) P.rb_lanes.push_back(l);
     if (!P.rb_lanes.empty()) {
+      const auto trb = Clock::now();
       const size_t m = P.rb_lanes.size();
-      const uint64_t stride = kFeedRegion;
       P.rb_lens.resize(m);
-      if (P.rb_bytes.size() < m * stride) P.rb_bytes.resize(m * stride);
-      if (wtfgpu_read_whole_feed_lanes(ctx_, P.rb_lanes.data(), (uint32_t)m, P.rb_lens.data(), P.rb_bytes.data(),
-                                       stride) != WTFGPU_OK)
+      P.rb_offs.resize(m);
+      uint64_t total = 0;
+      if (wtfgpu_read_feeds_packed(ctx_, P.rb_lanes.data(), (uint32_t)m, pkt_on_ ? 1 : 0, P.rb_lens.data(),
+                                   P.rb_offs.data(), &P.rb_bytes, &total) != WTFGPU_OK)
         return false;
-      P.rb_tcs.resize(m);
-      for (size_t k = 0; k < m; k++) {
-        if (P.rb_lens[k] > stride) return false;  // no feed (~0u)
-        P.rb_tcs[k] = pkt_.FeedToTestcase(P.rb_bytes.data() + k * stride, P.rb_lens[k]);
-      }
+      stats_.readback_ms += ms_since(trb);
+      const uint32_t longest = pkt_on_ ? (uint32_t)kFeedRegion : mut_max_len_;
+      for (size_t k = 0; k < m; k++)
+        if (P.rb_lens[k] > longest) return false;  // no feed (~0u), or not the mutator's chunk
+      if (pkt_on_) P.rb_tcs.resize(m);
       stats_.readback_tcs += m;
+      stats_.readback_bytes += total;
     }
   }
   const size_t base = Out.size();
@@ -2192,15 +2191,20 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
       Out[base + i] = StreamResult_t{tag_[l], nullptr, ex[l - first].icount};
     } else {
       Out[base + i] = StreamResult_t{tag_[l], &lres_[l]};
-      if ((mut_on_ || pkt_on_) && ordered_[l]) {  // its place in the read-back list (ascending, as finished is)
+      if ((mut_on_ || pkt_on_) && P.rb_keepf[i] == 1) {
+        // its place in the read-back list (ascending, as finished is); a packet
+        // list becomes the testcase the target keeps here, on the pool
         const size_t k = (size_t)(std::lower_bound(P.rb_lanes.begin(), P.rb_lanes.end(), l) - P.rb_lanes.begin());
+        const uint8_t *bytes = P.rb_bytes + P.rb_offs[k];
         if (pkt_on_) {
+          P.rb_tcs[k] = pkt_.FeedToTestcase(bytes, P.rb_lens[k]);
           Out[base + i].tc = (const uint8_t *)P.rb_tcs[k].data();
           Out[base + i].tc_size = P.rb_tcs[k].size();
         } else {
-          Out[base + i].tc = P.rb_bytes.data() + k * std::max<uint32_t>(mut_max_len_, 1);
+          Out[base + i].tc = bytes;
           Out[base + i].tc_size = P.rb_lens[k];
         }
+        Out[base + i].has_tc = true;
       }
     }
     busy_[l] = 0;  // not runnable until refilled (a finished lane keeps its exit status)
@@ -2250,10 +2254,12 @@ std::string GpuBackend_t::StatsJson() const {
   r.pop_back();
   snprintf(b, sizeof(b), ",\"up_prep_ms\":%.3f,\"up_regs_ms\":%.3f,\"up_apply_ms\":%.3f,\"up_feed_ms\":%.3f,"
            "\"restore_dev_ms\":%.3f,\"out_ms\":%.3f,\"fresh_ms\":%.3f,\"occ_ms\":%.3f,\"harvest_ms\":%.3f,"
-           "\"prepared\":%llu,\"device_attrib\":%d,\"mutate_dev_ms\":%.3f,\"readback_tcs\":%llu",
+           "\"prepared\":%llu,\"device_attrib\":%d,\"mutate_dev_ms\":%.3f,\"readback_tcs\":%llu,"
+           "\"readback_bytes\":%llu,\"readback_ms\":%.3f,\"readback_skipped\":%llu",
            stats_.up_prep_ms, stats_.up_regs_ms, stats_.up_apply_ms, stats_.up_feed_ms, stats_.restore_dev_ms,
            stats_.out_ms, stats_.fresh_ms, stats_.occ_ms, stats_.harvest_ms, (unsigned long long)stats_.prepared,
-           device_attrib_ ? 1 : 0, stats_.mutate_dev_ms, (unsigned long long)stats_.readback_tcs);
+           device_attrib_ ? 1 : 0, stats_.mutate_dev_ms, (unsigned long long)stats_.readback_tcs,
+           (unsigned long long)stats_.readback_bytes, stats_.readback_ms, (unsigned long long)stats_.readback_skipped);
   r += b;
   {  // the spill pool's counters (zero without one)
     wtfgpu_spill_stats_t sp{};

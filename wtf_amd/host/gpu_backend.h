@@ -51,6 +51,11 @@ struct BatchStats {
   double up_prep_ms = 0, up_regs_ms = 0, up_apply_ms = 0, up_feed_ms = 0, restore_dev_ms = 0;
   double mutate_dev_ms = 0;     // --device-mutate: wtfgpu_mutate_feed_lanes calls (host time; the kernel is asynchronous)
   uint64_t readback_tcs = 0;    // --device-mutate: testcases read back from the device
+  // the packed read-back (wtfgpu_read_feeds_packed): bytes moved (the calls'
+  // totals), time inside the calls, ordered non-plain results the session's
+  // filter left on the device
+  uint64_t readback_bytes = 0, readback_skipped = 0;
+  double readback_ms = 0;
   double out_ms = 0, fresh_ms = 0, occ_ms = 0, harvest_ms = 0;  // streaming: result hand-over, refill list, slice list, whole harvest
   // streaming harvest split: per-lane byte counters, coverage logs, attribution
   double bytes_ms = 0, covlog_ms = 0, attrib_ms = 0;
@@ -109,17 +114,19 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   bool CanStream() const override { return true; }
   bool TakesPrepared() const override { return feed_action_ || insert_action_; }
   // --device-mutate: ordered testcases are made by wtfgpu_mutate_feed_lanes at
-  // the refill, and the harvest reads back (wtfgpu_read_feed_lanes) the ones
-  // whose result is not the common counted one
+  // the refill, and the harvest reads back, packed (wtfgpu_read_feeds_packed),
+  // the ones whose result is not the common counted one and that the
+  // session's filter keeps
   bool HasDeviceMutator() const override { return true; }
   bool MutatesOnDevice() const override { return mut_on_ || pkt_on_; }
   bool SetDeviceMutate(uint64_t Seed, uint32_t MaxLen, uint64_t MaxEntries, uint64_t MaxBytes) override;
   bool DeviceCorpusAdd(const uint8_t *P, size_t N) override;
-  // --device-packets: the same with wtfgpu_mutate_packets_lanes and
-  // wtfgpu_read_whole_feed_lanes; a feed read back becomes the testcase
+  // --device-packets: the same with wtfgpu_mutate_packets_lanes and the
+  // lanes' whole feeds; a feed read back becomes the testcase
   // (PacketMutator_t::FeedToTestcase) before the session sees it
   bool SetDevicePackets(uint64_t Seed, const PacketMutator_t &M, uint64_t MaxEntries, uint64_t MaxBytes) override;
   bool DeviceCorpusAddFeed(const uint8_t *P, size_t N) override;
+  void SetReadbackFilter(std::function<bool(const LaneResult &)> F) override { rb_keep_ = std::move(F); }
   uint32_t FreeLanes() const override;
   bool StreamStep(const Target_t &Target, const std::vector<StreamTestcase_t> &In, uint64_t Slice,
                   std::vector<StreamResult_t> &Out, ModuleSlots *Slots, size_t *Taken) override;
@@ -317,10 +324,13 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
     uint64_t ex_cap = 0;
     uint8_t *pin = nullptr;
     uint64_t pin_cap = 0;
-    // --device-mutate: the testcases the last harvest read back (lens, bytes
-    // at a stride of mut_max_len_), valid until the part's next harvest
+    // --device-mutate: the testcases the last harvest read back (lens and
+    // offsets into the engine's pinned buffer of the part's queue, rb_bytes),
+    // valid until the part's next harvest
     std::vector<uint32_t> rb_lanes, rb_lens;
-    std::vector<uint8_t> rb_bytes;
+    std::vector<uint64_t> rb_offs;
+    std::vector<uint8_t> rb_keepf;  // per finished lane: the filter's answer
+    const uint8_t *rb_bytes = nullptr;
     std::vector<std::string> rb_tcs;  // --device-packets: the testcases made of the feeds read back
     // the slice's read-back queued behind it (wtfgpu_prefetch_results /
     // _coverage), pinned: byte and dirty-page counts, StopWithArgs
@@ -376,6 +386,7 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   std::vector<uint64_t> mut_idx_;
   // --device-packets: on, and the target's declaration (the stream's params, FeedToTestcase)
   bool pkt_on_ = false;
+  std::function<bool(const LaneResult &)> rb_keep_;  // SetReadbackFilter (empty: keep all)
   PacketMutator_t pkt_{};
   bool insert_action_ = false;                   // the declared insert is on the device (wtfgpu_set_insert)
   int upload_feed(uint32_t n);                   // lanes [0, n)

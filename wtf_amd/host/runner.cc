@@ -735,6 +735,12 @@ bool FuzzSession::Start() {
     Sample_ = fopen(O_.sample.c_str(), "w");
     if (!Sample_) return false;
   }
+  // An executor that makes testcases on its device reads back only what
+  // AccountStep will look at. CrashNames_ grows only in Account, on this
+  // thread, between two StreamStep calls: the harvest that asks runs inside
+  // StreamStep, so it reads the set while nothing writes it, and a name known
+  // then is still known when the same results are classified.
+  Exec_.SetReadbackFilter([this](const LaneResult &L) { return KeepsTestcase(&L, Sample_ != nullptr, CrashNames_); });
   fs::create_directories(T_ / "outputs");
   fs::create_directories(T_ / "crashes");
   if (Target_.CreateMutator) Mutator_ = Target_.CreateMutator(Rng_, O_.max_len);
@@ -1201,16 +1207,12 @@ bool FuzzSession::AccountStep(std::vector<StreamResult_t> &Out) {
         continue;
       }
       uint8_t k = 0;
-      if (every || L->error) {
+      if (KeepsTestcase(L, every, CrashNames_)) {  // (the decision a device executor's read-back filter makes too)
         k = K_SERIAL;
       } else {
         if (std::holds_alternative<Timedout_t>(L->result)) k |= K_TIMEOUT;
         if (std::holds_alternative<Cr3Change_t>(L->result)) k |= K_CR3;
-        if (const Crash_t *Cr = std::get_if<Crash_t>(&L->result)) {
-          k |= K_CRASH;
-          if (!Cr->CrashName.empty() && !CrashNames_.count(Cr->CrashName)) k = K_SERIAL;  // a new name
-        }
-        if (!L->new_coverage.empty() && !std::holds_alternative<Timedout_t>(L->result)) k = K_SERIAL;
+        if (std::holds_alternative<Crash_t>(L->result)) k |= K_CRASH;
       }
       if (k == K_SERIAL) {
         C.serial.push_back({(uint32_t)i, R});
@@ -1232,7 +1234,10 @@ bool FuzzSession::AccountStep(std::vector<StreamResult_t> &Out) {
       serial++;
       if (!F.r) Plain.icount = F.icount;
       if (E.second.ordered()) {  // made on the device: the executor read its bytes back
-        if (!F.r || (!F.tc && F.tc_size)) return false;
+        // (a result the executor's read-back filter left out has no bytes: the
+        // filter and the classification above are one function over the same
+        // names, so this is a defect, not a testcase of zero bytes)
+        if (!F.r || !F.has_tc || (!F.tc && F.tc_size)) return false;
         Account(F.tc, F.tc_size, *F.r, false);
         continue;
       }

@@ -8,6 +8,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <filesystem>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <cstdint>
@@ -68,10 +69,28 @@ struct StreamResult_t {
   LaneResult *r;
   uint64_t icount = 0;  // with r == nullptr
   // an ordered testcase (StreamTestcase_t::ordered) with r != nullptr: its
-  // bytes, read back from the device; valid as long as r is
+  // bytes, read back from the device; valid as long as r is. has_tc: they
+  // were read (tc_size may be 0); an executor with a read-back filter
+  // (SetReadbackFilter) reads only the results the filter keeps
   const uint8_t *tc = nullptr;
   size_t tc_size = 0;
+  bool has_tc = false;
 };
+
+// Does the session look at this result's testcase bytes? The one decision
+// behind FuzzSession::AccountStep's serial results and a device executor's
+// read-back: an engine error (kept under errors/), new coverage on a result
+// that did not time out (joins the corpus), a crash whose name is not known
+// yet (saved under crashes/), and every result while samples are written.
+// L == nullptr: the common counted result.
+inline bool KeepsTestcase(const LaneResult *L, bool Every, const std::unordered_set<std::string> &KnownCrashes) {
+  if (Every) return true;
+  if (!L) return false;
+  if (L->error) return true;
+  if (const Crash_t *Cr = std::get_if<Crash_t>(&L->result))
+    if (!Cr->CrashName.empty() && !KnownCrashes.count(Cr->CrashName)) return true;
+  return !L->new_coverage.empty() && !std::holds_alternative<Timedout_t>(L->result);
+}
 
 // A backend that runs many testcases per call (GpuBackend_t; the oracle twin
 // runs them one after the other).
@@ -108,6 +127,13 @@ class Executor_t {
     return false;
   }
   virtual bool DeviceCorpusAddFeed(const uint8_t *, size_t) { return false; }
+  // Which ordered results the session wants bytes for (KeepsTestcase over its
+  // own state): an executor that mutates on the device reads back only those
+  // and sets StreamResult_t::has_tc on them. Called during StreamStep, on any
+  // of the executor's host threads, never while the session accounts results.
+  // Not set: every ordered result that is not the common counted one is read.
+  // Default: nothing to filter.
+  virtual void SetReadbackFilter(std::function<bool(const LaneResult &)>) {}
   virtual uint32_t FreeLanes() const { return 0; }
   virtual bool StreamStep(const Target_t &, const std::vector<StreamTestcase_t> &, uint64_t,
                           std::vector<StreamResult_t> &, ModuleSlots *, size_t *Taken) {
