@@ -5,6 +5,7 @@
 // fast_exec, engine_fast.h) and falls back to exec() on a miss, as k_run does.
 #include <cstdlib>
 #include <vector>
+#include "../../wtf_amd/csrc/engine_deliver.h"
 #include "../../wtf_amd/csrc/engine_fast.h"
 #include "../../wtf_amd/csrc/engine_ptmark.h"
 using namespace wtfgpu_dev;
@@ -72,6 +73,7 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
   P.fs_base = fsb.data();
   P.gs_base = gsb.data();
   P.limit = limit;
+  P.cr3_0 = r0->cr3;  // as engine.hip: a write of another cr3 ends the lane
   wtfgpu_regs_t full = *r0;  // cold state: XMM registers, MXCSR
   LaneSys sys{};  // as engine.hip make_init
   sys.cr0 = r0->cr0;
@@ -136,6 +138,12 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
     g_tn = TenetDev{g_tn_store.data(), g_tn_store.size(), &g_tn_pos, &g_tn_cpos, &g_tn_ipos, &g_tn_last, &g_tn_mute};
     tn_regs(P, L);  // the registers at the start
   }
+  // a fault goes through the guest IDT where it has a gate, as in k_run; else the lane exits with it
+  auto delivered = [&]() {
+    if (L.status != WTFGPU_EXIT_FAULT || L.nodeliver || !deliver_fault(P, L)) return false;
+    if (g_tn.buf) tn_regs(P, L);
+    return true;
+  };
   for (uint64_t steps = 0; steps < 100000000 && L.status == WTFGPU_RUNNING; steps++) {
     const uint64_t grip = L.rip;
     uint64_t td;
@@ -144,7 +152,10 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
       else td = 0;
       if (!td && L.status == WTFGPU_EXIT_FAULT) L.exaddr = grip;
     }
-    if (!td) break;
+    if (!td) {
+      if (delivered()) continue;
+      break;
+    }
     const uint8_t *page = (const uint8_t *)(uintptr_t)(td & ~0xfffull);
     const uint32_t off = grip & 0xfff;
     IBytes ib;
@@ -162,7 +173,10 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
         if (service_miss(P, L, va2, ACC_X)) tlb_get(L, va2 >> 12, td);
         else td = 0;
       }
-      if (!td) break;
+      if (!td) {
+        if (delivered()) continue;
+        break;
+      }
       memcpy(bytes + ib.avail, (const uint8_t *)(uintptr_t)(td & ~0xfffull), 16 - ib.avail);
       memcpy(&ib.lo, bytes, 8);
       memcpy(&ib.hi, bytes + 8, 8);
@@ -171,6 +185,7 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
     }
     if (dr == 2) {
       set_fault(L, WTFGPU_VEC_GP, 0, 0);
+      if (delivered()) continue;
       break;
     }
     if (!d.supported) {
@@ -217,11 +232,12 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
       tlb_flush(L);
       L.flush = 0;
     }
-    if (x == X_OK && L.status == WTFGPU_RUNNING) {
+    if ((x == X_OK || x == X_CR3) && L.status == WTFGPU_RUNNING) {  // as engine_run.h retire()
       L.rip = next;
       L.icount++;
       L.nbytes += d.len + L.pend;
       if (P.limit && L.icount > P.limit) L.status = WTFGPU_EXIT_TIMEOUT;
+      else if (x == X_CR3) L.status = WTFGPU_EXIT_CR3;
       if (g_tn.buf) tn_regs(P, L);
     } else if (L.status != WTFGPU_RUNNING) {
     } else if (x == X_UNIMPL) {
@@ -231,6 +247,7 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
     } else if (x == X_HLT) {
       L.status = WTFGPU_EXIT_HLT;
     }
+    delivered();
   }
   if (g_tn.buf && g_tn_pos > g_tn_ipos) tn_regs(P, L);  // open accesses of the stopping instruction
   g_tn = TenetDev{};

@@ -161,6 +161,14 @@ def test_gpu_matches_x87_vectors():
     _replay(V.X87)
 
 
+def test_gpu_matches_x87_directed_vectors():
+    """The single-form x87 instructions by operand class (tests/golden/
+    x87_directed_vectors.json.gz; tests/test_x87.py counts the classes): fsqrt,
+    frndint, fscale, fprem / fprem1, fxtract, fxam and the integer stores at
+    their rounding, range and exception edges, one case per lane."""
+    _replay(V.X87D)
+
+
 def test_gpu_matches_native_ext_vectors():
     """BMI1 / BMI2 / ADX / MOVBE / CRC32, SSE4.2, AES, PCLMULQDQ (tests/golden/ext_vectors.json.gz, U45)."""
     _replay(V.EXT)

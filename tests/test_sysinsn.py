@@ -1,6 +1,7 @@
 """Ring-0 system instructions: the oracle's semantics on
-hand-checked cases (CPU), and the GPU engine against the oracle lane by lane on
-random operands (-m gpu): exit, rip, retired count, GPRs, RFLAGS, control
+hand-checked cases (CPU), and the engine against the oracle lane by lane on
+random operands, its lane code built for the host (CPU) and k_run (-m gpu):
+exit, rip, retired count, GPRs, RFLAGS, control
 registers, MSRs, selectors, coverage and dirty pages."""
 import pytest
 
@@ -69,6 +70,26 @@ def test_iretq(space):
     assert tsd["rip"] == space[2]["nt!SwapContext"]                     # ring-3 #GP ends the thread
     null_cs = _one(space, "iret", r13=st["cr4"], r8=0x18, r9=S.KSP, r10=0x202, r11=0, r12=S.HLT_TARGET)
     assert null_cs["rip"] == space[2]["nt!KeBugCheck2"] and null_cs["gpr"][1] == 0x1E
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_engine_lane_code_matches_oracle(space, seed):
+    """The engine's lane code built for the host against the oracle, lane by
+    lane on the GPU test's lanes: exit, rip, retired count, GPRs, RFLAGS, control
+    registers, MSRs, selectors and dirty pages."""
+    sp, st, _ = space
+    ln = S.lanes(512, seed, st)
+    want = S.oracle_run(sp, st, ln)
+    got = S.sim_run(sp, st, ln)
+    names = {v: k for k, v in S.SLOT.items()}
+    bad = []
+    for i, (w, g) in enumerate(zip(want, got, strict=True)):
+        f = w["status"] == FAULT
+        d = [k for k in g if g[k] != w[k] and (f or k not in ("vector", "error", "addr"))]
+        if d:
+            bad.append((i, names[ln[i][0]], d, {k: (g[k], w[k]) for k in d if k != "regs"}))
+    assert not bad, f"{len(bad)}/{len(ln)} lanes differ; first: {bad[:3]}"
+    assert len({(w["status"], w["rip"]) for w in want}) >= 6
 
 
 @pytest.mark.gpu

@@ -434,9 +434,10 @@ SSE4 = FpFormat("sse4", _FP + ("mem",), lambda i, c: bool(c.get("mdiff")), _sse4
 EXT = FpFormat("ext", _FP + ("mem",), lambda i, c: bool(c.get("mdiff")), _ext_inputs)
 AVX2X = FpFormat("avx2x", _FP + ("mem",), lambda i, c: bool(c.get("mdiff")), _avx2x_inputs)
 X87 = X87Stack("x87", ("status", "icount", "flags", "rip", "vec", "x87", "mem", "fault"), _every)
+X87D = X87Stack("x87_directed", X87.fields, _every)   # the single-form instructions by operand class
 AVX512 = Evex("avx512", _EVEX, _every, _avx512_inputs)
 AVX512X = Evex("avx512x", _EVEX, _every, _avx512x_inputs)
-FAMILIES = (NATIVE, SSE, MMX, AVX, FP, SSE4, EXT, AVX2X, X87, AVX512, AVX512X)
+FAMILIES = (NATIVE, SSE, MMX, AVX, FP, SSE4, EXT, AVX2X, X87, X87D, AVX512, AVX512X)
 
 
 # ---------------------------------------------------------------- executors

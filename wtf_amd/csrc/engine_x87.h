@@ -12,7 +12,9 @@
 // QNaN propagation (x87 rule: the larger significand), DE, ZE, OE, UE, PE.
 // Masked: the default result. Unmasked IE / DE / ZE: no result, no pop;
 // unmasked OE / UE: the result with its exponent wrapped by 24576 (register
-// destinations; a memory destination is not written). Any unmasked exception
+// destinations; a memory destination is not written; an fscale result that
+// the wrap leaves out of range is a signed infinity with C1 = 1 above, a
+// signed zero below). Any unmasked exception
 // sets ES and B; the next waiting x87 instruction then takes #MF first.
 // FOP / FIP / FDP are not maintained (U32). The transcendental forms (f2xm1,
 // fyl2x, fptan, fpatan, fyl2xp1, fsincos, fsin, fcos) stay UNIMPLEMENTED.
@@ -116,7 +118,9 @@ __device__ __noinline__ F80 x_round(XEnv &v, u32 s, i32 exp, u128 W, u32 prec) {
       v.fl |= SW_OE;
     } else {
       v.fl |= SW_OE | SW_PE;
-      if (inc) {
+      // unmasked and still out of range after the wrap (fscale alone gets here):
+      // a signed infinity whatever RC says, as the host CPU delivers it
+      if (inc || !(v.masks & SW_OE)) {
         v.c1 = 1;
         return x_inf(s);
       }
