@@ -414,6 +414,23 @@ int wtfgpu_corpus_add_feed(wtfgpu_ctx *ctx, const uint8_t *feed, uint64_t len, u
 int wtfgpu_mutate_packets_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint64_t seed,
                                 const uint64_t *indices, const uint32_t *ncorpus,
                                 const wtfgpu_packet_params_t *params);
+/* The minimiser's candidates (`wtfgpu minimize`): lane lanes[i] gets candidate
+ * indices[i] of op `op` over arena entry `entry`, as csrc/engine_minimize.h
+ * defines the stream. Over a byte-buffer arena the lane's feed is one chunk, as
+ * wtfgpu_mutate_feed_lanes writes it; over an arena of feeds it is the whole
+ * feed, as wtfgpu_mutate_packets_lanes writes it. A declared insert then runs
+ * on the same list, ordered after it, as in wtfgpu_mutate_feed_lanes.
+ * Asynchronous on the current queue; no caller's buffer is read after it
+ * returns. WTFGPU_ERR_INVALID, before anything is queued, for no arena, an
+ * `entry` at or above the entries added, a byte-buffer entry longer than
+ * WTFGPU_FEED_STRIDE - 4, an indices[i] at or above the entry's candidate
+ * count T(U) (U: its bytes, or its packets), a lane outside the context, an
+ * unknown op or a null pointer; WTFGPU_ERR_STATE for WTFGPU_MIN_ZERO on an
+ * arena of feeds. */
+#define WTFGPU_MIN_REMOVE 0u /* the base without the candidate's range */
+#define WTFGPU_MIN_ZERO 1u   /* byte buffers: the range's bytes set to 0 */
+int wtfgpu_minimize_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t entry, uint32_t op,
+                               const uint64_t *indices);
 /* As wtfgpu_read_feed_lanes, but the lane's whole feed, every chunk, from its
  * region's first byte to the feed's end (the feed stays in place while the
  * lane consumes it, until the lane's next feed). */

@@ -88,6 +88,7 @@ class PacketParams(C.Structure):
 
 
 ERR_INVALID, ERR_STATE, ERR_FULL = -1, -5, -7
+MIN_REMOVE, MIN_ZERO = 0, 1  # wtfgpu_minimize_feed_lanes' ops
 FEED_STRIDE = 16384  # WTFGPU_FEED_STRIDE: a testcase chunk is at most FEED_STRIDE - 4 bytes
 
 SEG_ORDER = ["es", "cs", "ss", "ds", "fs", "gs", "tr", "ldtr"]
@@ -200,6 +201,7 @@ def load_hip_library(path: str = LIB_PATH) -> C.CDLL:
         "wtfgpu_corpus_add_feed": ([P, C.c_char_p, U64, C.POINTER(U32)], C.c_int),
         "wtfgpu_mutate_packets_lanes": ([P, C.POINTER(U32), U32, U64, C.POINTER(U64), C.POINTER(U32),
                                          C.POINTER(PacketParams)], C.c_int),
+        "wtfgpu_minimize_feed_lanes": ([P, C.POINTER(U32), U32, U32, U32, C.POINTER(U64)], C.c_int),
         "wtfgpu_read_whole_feed_lanes": ([P, C.POINTER(U32), U32, C.POINTER(U32), P, U64], C.c_int),
         "wtfgpu_read_feeds_packed": ([P, C.POINTER(U32), U32, U32, C.POINTER(U32), C.POINTER(U64), C.POINTER(P),
                                       C.POINTER(U64)], C.c_int),

@@ -129,6 +129,9 @@ struct wtfgpu_ctx {
   u64 *d_corpus_off = nullptr;
   u64 corpus_max_entries = 0, corpus_max_bytes = 0;
   std::vector<u64> corpus_off;
+  // each entry's units (a byte buffer's bytes, a feed's packets): the index
+  // check of wtfgpu_minimize_feed_lanes (engine_minimize.h)
+  std::vector<u32> corpus_units;
   // what the arena holds, fixed by its first add: byte buffers
   // (wtfgpu_corpus_add) or indexed feeds (wtfgpu_corpus_add_feed)
   enum CorpusKind : u32 { kCorpusEmpty, kCorpusBytes, kCorpusFeeds } corpus_kind = kCorpusEmpty;
@@ -1099,6 +1102,7 @@ int wtfgpu_corpus_alloc(wtfgpu_ctx *c, uint64_t max_entries, uint64_t max_bytes)
   dfree(c->d_corpus_off);
   c->corpus_max_entries = c->corpus_max_bytes = 0;
   c->corpus_off.clear();
+  c->corpus_units.clear();
   c->corpus_kind = wtfgpu_ctx::kCorpusEmpty;
   if (max_entries == 0) return WTFGPU_OK;
   if (dalloc(&c->d_corpus, max_bytes) || dalloc(&c->d_corpus_off, max_entries + 1)) {
@@ -1126,6 +1130,7 @@ int wtfgpu_corpus_add(wtfgpu_ctx *c, const uint8_t *bytes, uint64_t len, uint32_
   const u64 end = used + len;
   HIPCHK(hipMemcpy(c->d_corpus_off + count + 1, &end, 8, hipMemcpyHostToDevice));
   c->corpus_off.push_back(end);
+  c->corpus_units.push_back((u32)std::min<u64>(len, 0xffffffffull));
   c->corpus_kind = wtfgpu_ctx::kCorpusBytes;
   if (index) *index = (u32)count;
   return WTFGPU_OK;
@@ -1148,6 +1153,7 @@ int wtfgpu_corpus_add_feed(wtfgpu_ctx *c, const uint8_t *feed, uint64_t len, uin
   const u64 end = used + bytes;
   HIPCHK(hipMemcpy(c->d_corpus_off + count + 1, &end, 8, hipMemcpyHostToDevice));
   c->corpus_off.push_back(end);
+  c->corpus_units.push_back((u32)packets);
   c->corpus_kind = wtfgpu_ctx::kCorpusFeeds;
   if (index) *index = (u32)count;
   return WTFGPU_OK;
@@ -1239,6 +1245,44 @@ int wtfgpu_mutate_packets_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n
   c->P.feed_pos = c->d_feedpos;
   c->P.feed_end = c->d_feedend;
   c->P.feed_data = c->d_feeddata;
+  return WTFGPU_OK;
+}
+
+// The minimiser's candidates (engine_minimize.h): as wtfgpu_mutate_feed_lanes,
+// with the orders checked against the entry's unit count the host keeps.
+int wtfgpu_minimize_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32_t entry, uint32_t op,
+                               const uint64_t *indices) {
+  if (!c || !c->d_gpr || !c->d_corpus || (n && (!lanes || !indices)) || op >= wtfmin::kNumOps ||
+      entry >= c->corpus_units.size() || !lane_list_in_range(c, lanes, n))
+    return WTFGPU_ERR_INVALID;
+  const bool feeds = c->corpus_kind == wtfgpu_ctx::kCorpusFeeds;
+  const u32 units = c->corpus_units[entry];
+  // a byte buffer goes out as one chunk behind its u32 size: the kernel checks nothing
+  if (!feeds && c->corpus_off[entry + 1] - c->corpus_off[entry] > WTFGPU_FEED_STRIDE - 4) return WTFGPU_ERR_INVALID;
+  {
+    const u64 total = wtfmin::total(units);
+    u32 bad = 0;
+    for (u32 i = 0; i < n; i++) bad |= (u32)(indices[i] >= total);
+    if (bad) return WTFGPU_ERR_INVALID;
+  }
+  if (feeds && op == wtfmin::kZero) return WTFGPU_ERR_STATE;
+  if (n == 0) return WTFGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = feed_regions(c)) return rc;
+  Side s[] = {side_in(indices, (u64)n * 8)};
+  if (int rc = stage_lanes(c, Upload::Ring, lanes, n, s, 1)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_minimize_feeds<<<(n + MUT_WAVES - 1) / MUT_WAVES, 64 * MUT_WAVES, 0, c->q->stream>>>(
+      c->d_feeddata, c->feed_stride, (const u32 *)S, (const u64 *)(S + s[0].off), n, entry, op, feeds ? 1u : 0u,
+      c->d_corpus, c->d_corpus_off, c->d_feedpos, c->d_feedend);
+  HIPCHK(hipGetLastError());
+  c->P.feed_pos = c->d_feedpos;
+  c->P.feed_end = c->d_feedend;
+  c->P.feed_data = c->d_feeddata;
+  if (c->ins_on) {  // the declared insert of the listed lanes, ordered after the candidates
+    k_insert<<<(n + 63) / 64, 64, 0, c->q->stream>>>(c->P, c->ins, (const u32 *)S, 0, n);
+    HIPCHK(hipGetLastError());
+  }
   return WTFGPU_OK;
 }
 

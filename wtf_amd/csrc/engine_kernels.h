@@ -6,6 +6,7 @@
 #include "engine_run.h"
 #include "engine_mutate.h"
 #include "engine_mutate_packets.h"
+#include "engine_minimize.h"
 #include "engine_feedpack.h"
 
 namespace {
@@ -673,6 +674,48 @@ __global__ __launch_bounds__(64 * MUT_WAVES) void k_mutate_packets(u8 *feed, u64
   if (l == 0) {
     feed_pos[lane] = (u64)lane * stride;
     feed_end[lane] = (u64)lane * stride + size;
+  }
+}
+
+// The minimiser's candidates (wtfgpu_minimize_feed_lanes; engine_minimize.h
+// defines the stream): one wave per candidate, MUT_WAVES a block, as the two
+// mutators. Candidate i is index[i] of `op` over arena entry `entry`; its
+// level, range and plan depend on those alone, so all 64 lanes compute the
+// same plan and then write four bytes a lane a round. A byte-buffer arena
+// (feeds == 0) gets the chunk k_mutate_feeds writes: a little-endian u32 size
+// and the bytes from region + 4, the last word zero-padded inside the region
+// (size <= stride - 4: the call refuses a longer entry). A feed arena gets the
+// whole feed from the region's first byte, as k_mutate_packets writes it
+// (size <= stride). The tail is the base shifted by any byte count, so its
+// words are composed byte by byte through the plan; a head word is loaded
+// whole only where it lies wholly in the head and its source is 4-aligned
+// (the destination always is). No LDS, and the plan stays in registers.
+__global__ __launch_bounds__(64 * MUT_WAVES) void k_minimize_feeds(u8 *feed, u64 stride, const u32 *lanes,
+                                                                   const u64 *index, u32 n, u32 entry, u32 op,
+                                                                   u32 feeds, const u8 *arena, const u64 *arena_off,
+                                                                   u64 *feed_pos, u64 *feed_end) {
+  const u32 i = blockIdx.x * MUT_WAVES + threadIdx.x / 64, l = threadIdx.x & 63;
+  if (i >= n) return;
+  const u32 lane = lanes[i];
+  wtfmin::Plan p;
+  wtfmin::make_plan(p, wtfmut::Corpus{arena, arena_off}, entry, feeds != 0, op, index[i]);
+  const u32 skip = feeds ? 0 : 4;
+  u8 *dst = feed + (u64)lane * stride;
+  if (l == 0) {
+    feed_pos[lane] = (u64)lane * stride;
+    feed_end[lane] = (u64)lane * stride + skip + p.size;
+    if (!feeds) *(u32 *)dst = p.size;
+  }
+  const bool aligned = ((u64)p.base & 3) == 0;
+  for (u32 j = 4 * l; j < p.size; j += 256) {
+    u32 w = 0;
+    if (aligned && j + 4 <= p.a) {
+      w = *(const u32 *)(p.base + j);
+    } else {
+      for (u32 k = 0; k < 4; k++)
+        if (j + k < p.size) w |= (u32)wtfmin::plan_byte(p, j + k) << (8 * k);
+    }
+    *(u32 *)(dst + skip + j) = w;
   }
 }
 

@@ -179,6 +179,22 @@ class Engine:
     def mutate_packets_lanes(self, lanes, seed, indices, ncorpus, params):
         _chk(self.mutate_packets_lanes_rc(lanes, seed, indices, ncorpus, params), "mutate_packets_lanes")
 
+    # ---- the minimiser's candidates (csrc/engine_minimize.h)
+    def minimize_feed_lanes_rc(self, lanes, entry, op, indices) -> int:
+        """wtfgpu_minimize_feed_lanes' return code (asynchronous on the queue);
+        op: abi.MIN_REMOVE or abi.MIN_ZERO. lanes / indices None: a null pointer."""
+        la = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.uint32)
+        ix = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint64)
+        n = len(la) if la is not None else len(ix)
+        assert la is None or ix is None or len(ix) == len(la)
+        return self.L.wtfgpu_minimize_feed_lanes(self.ctx,
+                                                 None if la is None else la.ctypes.data_as(C.POINTER(C.c_uint32)), n,
+                                                 entry, op,
+                                                 None if ix is None else ix.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def minimize_feed_lanes(self, lanes, entry, op, indices):
+        _chk(self.minimize_feed_lanes_rc(lanes, entry, op, indices), "minimize_feed_lanes")
+
     def read_whole_feed_lanes(self, lanes, stride=abi.FEED_STRIDE):
         """Each listed lane's whole feed (None: the lane has no feed)."""
         la = np.ascontiguousarray(lanes, dtype=np.uint32)

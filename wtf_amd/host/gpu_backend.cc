@@ -308,6 +308,30 @@ bool GpuBackend_t::DeviceCorpusAddFeed(const uint8_t *P, size_t N) {
   return pkt_on_ && wtfgpu_corpus_add_feed(ctx_, P, N, nullptr) == WTFGPU_OK;
 }
 
+// `minimize`: a small arena for the bases, one a round. Byte buffers reach the
+// guest through the declared insert, feeds through the Feed action: without
+// the one the target needs on the device, candidates made there go nowhere.
+constexpr uint64_t kMinArenaEntries = 256, kMinArenaBytes = 4ull << 20;
+bool GpuBackend_t::SetDeviceMinimize(bool Feeds) {
+  if (mut_on_ || pkt_on_ || !(Feeds ? feed_action_ : insert_action_)) return false;
+  if (wtfgpu_corpus_alloc(ctx_, kMinArenaEntries, kMinArenaBytes) != WTFGPU_OK) return false;
+  min_on_ = true;
+  min_feeds_ = Feeds;
+  return true;
+}
+
+// The round's base. A full arena is dropped and allocated anew: the call comes
+// at a round boundary, when no lane holds a candidate of an earlier base.
+bool GpuBackend_t::DeviceMinimizeBase(const uint8_t *P, size_t N, uint32_t *Entry) {
+  if (!min_on_) return false;
+  for (int Try = 0; Try < 2; Try++) {
+    const int rc = min_feeds_ ? wtfgpu_corpus_add_feed(ctx_, P, N, Entry) : wtfgpu_corpus_add(ctx_, P, N, Entry);
+    if (rc == WTFGPU_OK) return true;
+    if (rc != WTFGPU_ERR_FULL || wtfgpu_corpus_alloc(ctx_, kMinArenaEntries, kMinArenaBytes) != WTFGPU_OK) return false;
+  }
+  return false;
+}
+
 // The testcase as the feed's one chunk (u32 size, bytes); the device applies
 // the declared insert to it before the lane runs.
 bool GpuBackend_t::SetInsert(const uint8_t *Data, const uint64_t Size) {
@@ -1801,9 +1825,14 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
     mut_lanes_.clear();
     mut_idx_.clear();
     mut_nc_.clear();
-    if (mut_on_ || pkt_on_)
+    uint32_t min_entry = 0, min_op = 0;  // `minimize`: one entry and op a step
+    if (mut_on_ || pkt_on_ || min_on_)
       for (size_t i = 0; i < n; i++)
         if (In[i].ordered) {
+          if (In[i].minimize != min_on_) return false;
+          if (min_on_ && !mut_lanes_.empty() && (In[i].min_entry != min_entry || In[i].min_op != min_op)) return false;
+          min_entry = In[i].min_entry;
+          min_op = In[i].min_op;
           mut_lanes_.push_back(fresh[i]);
           mut_idx_.push_back(In[i].index);
           mut_nc_.push_back(In[i].ncorpus);
@@ -1856,7 +1885,11 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
     }
     if (!mut_lanes_.empty()) {
       const auto tmu = Clock::now();
-      if (pkt_on_) {
+      if (min_on_) {
+        if (wtfgpu_minimize_feed_lanes(ctx_, mut_lanes_.data(), (uint32_t)mut_lanes_.size(), min_entry, min_op,
+                                       mut_idx_.data()) != WTFGPU_OK)
+          return false;
+      } else if (pkt_on_) {
         const wtfgpu_packet_params_t pp{pkt_.GenMaxPackets, pkt_.GenCommands, pkt_.GenMaxBody, pkt_.FlipOneIn,
                                         pkt_.InsertMaxPackets};
         if (wtfgpu_mutate_packets_lanes(ctx_, mut_lanes_.data(), (uint32_t)mut_lanes_.size(), mut_seed_,

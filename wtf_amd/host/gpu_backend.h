@@ -127,6 +127,11 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   bool SetDevicePackets(uint64_t Seed, const PacketMutator_t &M, uint64_t MaxEntries, uint64_t MaxBytes) override;
   bool DeviceCorpusAddFeed(const uint8_t *P, size_t N) override;
   void SetReadbackFilter(std::function<bool(const LaneResult &)> F) override { rb_keep_ = std::move(F); }
+  // `minimize`: a round's candidates are made by wtfgpu_minimize_feed_lanes at
+  // the refill, from the base added to the arena once a round; none is read back
+  bool HasDeviceMinimizer() const override { return true; }
+  bool SetDeviceMinimize(bool Feeds) override;
+  bool DeviceMinimizeBase(const uint8_t *P, size_t N, uint32_t *Entry) override;
   uint32_t FreeLanes() const override;
   bool StreamStep(const Target_t &Target, const std::vector<StreamTestcase_t> &In, uint64_t Slice,
                   std::vector<StreamResult_t> &Out, ModuleSlots *Slots, size_t *Taken) override;
@@ -388,6 +393,8 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   bool pkt_on_ = false;
   std::function<bool(const LaneResult &)> rb_keep_;  // SetReadbackFilter (empty: keep all)
   PacketMutator_t pkt_{};
+  // `minimize`: on, and whether the arena holds feeds (else byte buffers)
+  bool min_on_ = false, min_feeds_ = false;
   bool insert_action_ = false;                   // the declared insert is on the device (wtfgpu_set_insert)
   int upload_feed(uint32_t n);                   // lanes [0, n)
   std::unordered_set<uint64_t> aggregate_;

@@ -7,6 +7,9 @@
 //   wtfgpu master --name tlv_server --target targets/tlv --address tcp://127.0.0.1:31337 --nodes 8 --batched
 //   wtfgpu fuzz --name tlv_server --target targets/tlv --lanes 65536 --address tcp://127.0.0.1:31337 --batched
 //       (a master process and one node per GPU over the wire protocol, remote.h / wire.h)
+//   wtfgpu minimize --name hevd --target targets/hevd --input targets/hevd/crashes/crash-... [--output f]
+//       [--lanes 4096] [--limit l] [--rounds r]   (shrinks one crashing testcase, keeping its crash name;
+//       candidates made on the GPU, WTFGPU_MINIMIZE_HOST=1 uploads them instead: minimize.cc)
 // The same runner drives the oracle twin (oracle/twin_backend.cc) for parity.
 #include <cstdio>
 #include <memory>

@@ -232,6 +232,8 @@ void PrintTestcaseRunStats(const LaneResult &L, size_t AggregateCoverage) {
 }
 
 bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
+  bool Minimize = false;
+  int ModeWords = 0;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto next = [&](const char *what) -> const char * {
@@ -241,7 +243,10 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
       }
       return argv[++i];
     };
-    if (a == "run" || a == "fuzz" || a == "master") O.mode = a;
+    if (a == "run" || a == "fuzz" || a == "master") O.mode = a, ModeWords++;
+    else if (a == "minimize") Minimize = true;
+    else if (a == "--output") O.output = next("--output");
+    else if (a == "--rounds") O.rounds = strtoull(next("--rounds"), nullptr, 0);
     else if (a == "--name") O.name = next("--name");
     else if (a == "--target") O.target = next("--target");
     else if (a == "--input") O.input = next("--input");
@@ -294,6 +299,18 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     fprintf(stderr, "--rank must be in [0, --world)\n");
     return false;
   }
+  if (Minimize) {
+    if (ModeWords || !O.address.empty() || O.world > 1 || !O.module_so.empty()) {
+      fprintf(stderr, "minimize is one in-process session: not with master (or another mode), --address, --world > 1 "
+                      "or --module-so\n");
+      return false;
+    }
+    if (O.input.empty()) {
+      fprintf(stderr, "minimize needs --input <crashing testcase>\n");
+      return false;
+    }
+    O.mode = "minimize";
+  }
   if (O.mode == "master" && (O.address.empty() || O.nodes < 1)) {
     fprintf(stderr, "master needs --address and --nodes >= 1\n");
     return false;
@@ -317,12 +334,13 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     }
   }
   if (O.name.empty() || O.target.empty()) {
-    fprintf(stderr, "usage: [run|fuzz|master] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
+    fprintf(stderr, "usage: [run|fuzz|master|minimize] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
                     "       [--lanes n] [--overlay-pages k] [--spill-pages s [--spill-lane-max x]] [--runs n] [--seconds s] [--seed s] [--full-coverage]\n"
                     "       [--serial-mutation] [--slice-steps s] [--regroup-steps r] [--rank r --world n [--exchange host:port | --nccl-id-file f]]\n"
                     "       [--address tcp://ip:port|unix://path [--batched] [--nodes k]] [--edges] [--device-attrib] [--device-mutate]\n"
                     "       [--device-packets]\n"
-                    "       [--trace-path dir [--trace-type rip|cov|tenet] [--trace-cap n] [--tenet-cap bytes]] [--module-so m.so] [--serial]\n");
+                    "       [--trace-path dir [--trace-type rip|cov|tenet] [--trace-cap n] [--tenet-cap bytes]] [--module-so m.so] [--serial]\n"
+                    "       minimize: --input <crashing testcase> [--output f] [--lanes n] [--limit l] [--rounds r]\n");
     return false;
   }
   return true;
@@ -626,6 +644,8 @@ int RunnerMain(const RunnerOptions &O, Executor_t &Exec, const Options_t &Opts, 
               secs_since(t0));
     return 0;
   }
+
+  if (O.mode == "minimize") return MinimizeMain(O, Exec, *Target, Slots);
 
   // ---- fuzz against a remote master (wire.h): the client loop
   if (!O.address.empty()) return NodeMain(O, Exec, *Target, Slots);

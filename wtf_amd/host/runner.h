@@ -57,6 +57,12 @@ struct StreamTestcase_t {
   bool ordered = false;
   uint64_t index = 0;
   uint32_t ncorpus = 0;
+  // `minimize` on an executor with the device minimiser: an ordered testcase
+  // that is candidate `index` of `min_op` over the base the executor was given
+  // last (DeviceMinimizeBase gave `min_entry`; csrc/engine_minimize.h). Every
+  // order of one step names the same entry and op.
+  bool minimize = false;
+  uint32_t min_entry = 0, min_op = 0;
 };
 // A finished testcase: its tag and its result, which stays in the executor's
 // storage and is valid until the executor's next StreamStep (no per-result
@@ -127,6 +133,16 @@ class Executor_t {
     return false;
   }
   virtual bool DeviceCorpusAddFeed(const uint8_t *, size_t) { return false; }
+  // `minimize`: true = this executor makes a round's candidates itself
+  // (StreamTestcase_t::minimize) from the base it is given once a round, and
+  // reads no candidate back: the session re-derives the winner. Feeds: the
+  // bases are feeds (a target with a PacketMutator_t), else byte buffers put
+  // into the guest by the declared insert. SetDeviceMinimize false = it
+  // cannot serve this target so. DeviceMinimizeBase is called between rounds,
+  // when no candidate is in a lane. Default: the session materialises.
+  virtual bool HasDeviceMinimizer() const { return false; }
+  virtual bool SetDeviceMinimize(bool /*Feeds*/) { return false; }
+  virtual bool DeviceMinimizeBase(const uint8_t *, size_t, uint32_t * /*Entry*/) { return false; }
   // Which ordered results the session wants bytes for (KeepsTestcase over its
   // own state): an executor that mutates on the device reads back only those
   // and sets StreamResult_t::has_tc on them. Called during StreamStep, on any
@@ -249,11 +265,13 @@ class CoverageExchange_t {
 void PrintTestcaseRunStats(const LaneResult &L, size_t AggregateCoverage);
 
 struct RunnerOptions {
-  std::string mode = "run";  // run | fuzz | master
+  std::string mode = "run";  // run | fuzz | master | minimize
   std::string name;          // target name
   std::string target;        // dir with state/, inputs/, outputs/, crashes/
   std::string input;         // run: file or directory (default <target>/inputs)
   std::string results;       // run: JSON-lines output path
+  std::string output;        // minimize: where the minimised testcase goes (default <input>.min)
+  uint64_t rounds = 4096;    // minimize: the session stops after this many rounds
   uint64_t limit = 0;
   uint32_t lanes = 1;
   uint32_t overlay_pages = 32;
@@ -529,6 +547,11 @@ class FuzzSession {
   };
   std::vector<AcctChunk> Acct_;
 };
+
+// `minimize` (minimize.cc): shrinks the crashing testcase O.input, keeping its
+// crash name, with the candidate stream of csrc/engine_minimize.h; candidates
+// are made on the device where the executor can. Returns the exit code.
+int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, ModuleSlots &Slots);
 
 bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O);
 // A Tenet entry stream (include/wtfgpu.h wtfgpu_set_tenet) as the reference's
