@@ -431,6 +431,24 @@ int wtfgpu_mutate_packets_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t
 #define WTFGPU_MIN_ZERO 1u   /* byte buffers: the range's bytes set to 0 */
 int wtfgpu_minimize_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t entry, uint32_t op,
                                const uint64_t *indices);
+/* The corpus distiller (`wtfgpu distill`): a greedy cover of n coverage sets,
+ * as csrc/engine_distill.h defines the rule. Set i is the strictly ascending
+ * values[offsets[i], offsets[i + 1]); eligible[i] == 0 leaves it out
+ * (eligible == NULL: every set is in). In every round the eligible set that
+ * adds the most values not yet covered is taken, the lowest index among equal
+ * gains, until no set adds any: out_index[0, *kept) are the taken sets in the
+ * order taken, out_gain their gains (room for n each), *universe the number
+ * of distinct values over the eligible sets. All buffers are host buffers.
+ * Synchronous, on the selected queue's stream; it needs a context but no
+ * lanes and no snapshot, and everything it allocates is freed before it
+ * returns. n == 0 is WTFGPU_OK with *kept == 0. WTFGPU_ERR_INVALID, before
+ * anything is queued or allocated, for a null pointer with n > 0,
+ * offsets[0] != 0, offsets that decrease, more than 2^32 - 1 entries, or a
+ * set that is not strictly ascending; WTFGPU_ERR_OOM when an allocation
+ * fails. */
+int wtfgpu_distill(wtfgpu_ctx *ctx, uint32_t n, const uint64_t *offsets, const uint64_t *values,
+                   const uint8_t *eligible, uint32_t *out_index, uint32_t *out_gain, uint32_t *kept,
+                   uint64_t *universe);
 /* As wtfgpu_read_feed_lanes, but the lane's whole feed, every chunk, from its
  * region's first byte to the feed's end (the feed stays in place while the
  * lane consumes it, until the lane's next feed). */

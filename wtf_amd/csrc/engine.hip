@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/device/device_radix_sort.hpp>
 #include <hipcub/device/device_scan.hpp>
+#include <hipcub/device/device_select.hpp>
 
 #include <algorithm>
 #include <cstddef>
@@ -1283,6 +1284,102 @@ int wtfgpu_minimize_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n,
     k_insert<<<(n + 63) / 64, 64, 0, c->q->stream>>>(c->P, c->ins, (const u32 *)S, 0, n);
     HIPCHK(hipGetLastError());
   }
+  return WTFGPU_OK;
+}
+
+// The corpus distiller (engine_distill.h): what one call allocates, freed
+// whatever way the call ends.
+struct DistillBufs {
+  u64 *vals = nullptr, *sorted = nullptr, *uniq = nullptr, *count = nullptr;
+  u8 *temp = nullptr;
+  u32 *ids = nullptr, *off = nullptr, *gain = nullptr, *bitmap = nullptr, *out_index = nullptr, *out_gain = nullptr;
+  DistillState *st = nullptr;
+  ~DistillBufs() {
+    dfree(vals), dfree(sorted), dfree(uniq), dfree(count), dfree(temp), dfree(ids), dfree(off), dfree(gain);
+    dfree(bitmap), dfree(out_index), dfree(out_gain), dfree(st);
+  }
+};
+
+// The eligible sets go up packed, in rank order, so the device sees no flag
+// and its set k is the host's pick[k]: the lowest k among equal gains is the
+// lowest i. Dense ids: radix sort of a copy, unique, binary search. Then
+// rounds of k_distill_gain + k_distill_take, DIS_BATCH of them queued between
+// two looks at `done`; a call of m sets ends after at most m + 1 rounds.
+int wtfgpu_distill(wtfgpu_ctx *c, uint32_t n, const uint64_t *offsets, const uint64_t *values, const uint8_t *eligible,
+                   uint32_t *out_index, uint32_t *out_gain, uint32_t *kept, uint64_t *universe) {
+  if (!c) return WTFGPU_ERR_INVALID;
+  if (int rc = wtfdis::validate(n, offsets, values, out_index, out_gain, kept, universe)) return rc;
+  *kept = 0;
+  *universe = 0;
+  if (n == 0) return WTFGPU_OK;
+  std::vector<u32> pick, off(1, 0), size;
+  try {
+    for (u32 i = 0; i < n; i++) {
+      if (eligible && !eligible[i]) continue;
+      pick.push_back(i);
+      size.push_back((u32)(offsets[i + 1] - offsets[i]));
+      off.push_back(off.back() + size.back());
+    }
+  } catch (const std::bad_alloc &) {
+    return WTFGPU_ERR_OOM;
+  }
+  const u32 m = (u32)pick.size();
+  const u64 E = off.back();
+  if (E == 0) return WTFGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const hipStream_t stream = c->q->stream;
+  DistillBufs B;
+  size_t sort_bytes = 0, uniq_bytes = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const u64 *)nullptr, (u64 *)nullptr, E, 0, 64, stream));
+  HIPCHK(hipcub::DeviceSelect::Unique(nullptr, uniq_bytes, (const u64 *)nullptr, (u64 *)nullptr, (u64 *)nullptr,
+                                      (int64_t)E, stream));
+  if (dalloc(&B.vals, E) || dalloc(&B.sorted, E) || dalloc(&B.uniq, E) || dalloc(&B.count, 1) || dalloc(&B.ids, E) ||
+      dalloc(&B.off, (u64)m + 1) || dalloc(&B.gain, m) || dalloc(&B.out_index, m) || dalloc(&B.out_gain, m) ||
+      dalloc(&B.st, 1) || dalloc(&B.temp, std::max(sort_bytes, uniq_bytes)))
+    return WTFGPU_ERR_OOM;
+  for (u32 k = 0; k < m;) {  // a run of eligible neighbours is one copy
+    u32 e = k + 1;
+    while (e < m && pick[e] == pick[e - 1] + 1) e++;
+    if (off[e] > off[k])
+      HIPCHK(hipMemcpyAsync(B.vals + off[k], values + offsets[pick[k]], (u64)(off[e] - off[k]) * 8,
+                            hipMemcpyHostToDevice, stream));
+    k = e;
+  }
+  HIPCHK(hipMemcpyAsync(B.off, off.data(), ((u64)m + 1) * 4, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(B.gain, size.data(), (u64)m * 4, hipMemcpyHostToDevice, stream));  // a set's size bounds its gain
+  HIPCHK(hipMemsetAsync(B.st, 0, sizeof(DistillState), stream));
+  HIPCHK(hipcub::DeviceRadixSort::SortKeys(B.temp, sort_bytes, (const u64 *)B.vals, B.sorted, E, 0, 64, stream));
+  HIPCHK(hipcub::DeviceSelect::Unique(B.temp, uniq_bytes, (const u64 *)B.sorted, B.uniq, B.count, (int64_t)E, stream));
+  u64 U = 0;
+  HIPCHK(hipMemcpyAsync(&U, B.count, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (U == 0 || U > E) return WTFGPU_ERR_HIP;
+  const u64 words = U / 32 + 1;
+  if (dalloc(&B.bitmap, words)) return WTFGPU_ERR_OOM;
+  HIPCHK(hipMemsetAsync(B.bitmap, 0, words * 4, stream));
+  k_distill_ids<<<(u32)((E + DIS_BLOCK - 1) / DIS_BLOCK), DIS_BLOCK, 0, stream>>>(B.vals, E, B.uniq, (u32)U, B.ids);
+  HIPCHK(hipGetLastError());
+  const u32 gain_blocks = (u32)(((u64)m * DIS_GROUP + DIS_BLOCK - 1) / DIS_BLOCK);
+  DistillState st{};
+  for (u64 rounds = 0; !st.done;) {
+    if (rounds > m) return WTFGPU_ERR_HIP;  // (m sets end in m + 1 rounds)
+    const u64 batch = std::min<u64>(DIS_BATCH, (u64)m + 1 - rounds);
+    for (u64 r = 0; r < batch; r++) {
+      k_distill_gain<<<gain_blocks, DIS_BLOCK, 0, stream>>>(B.off, B.ids, m, B.bitmap, B.gain, B.st);
+      k_distill_take<<<1, DIS_BLOCK, 0, stream>>>(B.off, B.ids, B.bitmap, B.gain, B.st, B.out_index, B.out_gain);
+    }
+    HIPCHK(hipGetLastError());
+    rounds += batch;
+    HIPCHK(hipMemcpyAsync(&st, B.st, sizeof(st), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  if (st.kept > m) return WTFGPU_ERR_HIP;
+  HIPCHK(hipMemcpyAsync(out_index, B.out_index, (u64)st.kept * 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(out_gain, B.out_gain, (u64)st.kept * 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  for (u32 k = 0; k < st.kept; k++) out_index[k] = pick[out_index[k]];
+  *kept = st.kept;
+  *universe = U;
   return WTFGPU_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "engine_mutate.h"
 #include "engine_mutate_packets.h"
 #include "engine_minimize.h"
+#include "engine_distill.h"
 #include "engine_feedpack.h"
 
 namespace {
@@ -933,6 +934,89 @@ __global__ void k_attr_emit(const u64 *vals, const u32 *pos, const u32 *flag, co
   if (j >= s || !flag[j]) return;
   out_pos[at[j]] = pos[j];
   out_vals[at[j]] = vals[j];
+}
+
+// ---- the corpus distiller (wtfgpu_distill; engine_distill.h defines the rule)
+// The words a call's kernels share: the round's running maximum key (0: none
+// yet), `done` once a round found no gain, and how many sets are taken.
+struct DistillState {
+  u64 key;
+  u32 done, kept;
+};
+constexpr u32 DIS_GROUP = 16;   // lanes that count one set
+constexpr u32 DIS_BLOCK = 256;  // 16 sets a block
+constexpr u32 DIS_BATCH = 64;   // rounds queued between two looks at `done`
+
+// Each entry's dense id: its value's place in the sorted unique values.
+__global__ __launch_bounds__(DIS_BLOCK) void k_distill_ids(const u64 *vals, u64 entries, const u64 *uniq, u32 universe,
+                                                           u32 *ids) {
+  const u64 e = (u64)blockIdx.x * DIS_BLOCK + threadIdx.x;
+  if (e >= entries) return;
+  const u64 v = vals[e];
+  u32 lo = 0, hi = universe;
+  while (lo < hi) {
+    const u32 mid = lo + (hi - lo) / 2;
+    if (uniq[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  ids[e] = lo;
+}
+
+// One round's gains. DIS_GROUP lanes count one set: sets run from none to
+// 8,192 entries and most hold a few hundred, so a wave a set would idle most
+// lanes on the short ones, while 16 lanes still read 64 contiguous bytes of
+// ids a step and four sets share a wave. A group leaves at one load when its
+// set is dead (gain 0: `covered` only grows, so it stays 0) and at two when
+// the set's stale key is below the round's running maximum (engine_distill.h,
+// lazy evaluation; a running maximum read late only prunes less). The group's
+// lanes stay together (every condition is the group's), so a ballot's 16 bits
+// of the group are the step's absent ids. One atomicMax a counted set.
+__global__ __launch_bounds__(DIS_BLOCK) void k_distill_gain(const u32 *off, const u32 *ids, u32 sets,
+                                                            const u32 *bitmap, u32 *gain, DistillState *st) {
+  if (st->done) return;
+  const u64 t = (u64)blockIdx.x * DIS_BLOCK + threadIdx.x;
+  const u32 s = (u32)(t / DIS_GROUP), l = threadIdx.x % DIS_GROUP, shift = (threadIdx.x & 63) / DIS_GROUP * DIS_GROUP;
+  if (s >= sets) return;
+  const u32 stale = gain[s];
+  if (stale == 0) return;
+  const u64 running = __hip_atomic_load(&st->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (wtfdis::make_key(stale, s) < running) return;
+  const u64 lo = off[s], hi = off[s + 1];
+  u32 g = 0;
+  for (u64 b = lo; b < hi; b += DIS_GROUP) {
+    const u64 j = b + l;
+    const bool absent = j < hi && !wtfdis::covered(bitmap, ids[j]);
+    g += __popcll((__ballot(absent) >> shift) & ((1ull << DIS_GROUP) - 1));
+  }
+  if (l == 0) {
+    gain[s] = g;
+    if (g) atomicMax((unsigned long long *)&st->key, (unsigned long long)wtfdis::make_key(g, s));
+  }
+}
+
+// One round's take, one block: the key's set joins `covered` (ids of one set
+// share bitmap words: atomicOr), is appended to the output and marked dead;
+// no key means the cover is complete. The bitmap reaches the next round's
+// k_distill_gain through the kernel boundary.
+__global__ __launch_bounds__(DIS_BLOCK) void k_distill_take(const u32 *off, const u32 *ids, u32 *bitmap, u32 *gain,
+                                                            DistillState *st, u32 *out_index, u32 *out_gain) {
+  if (st->done) return;
+  const u64 key = st->key;
+  __syncthreads();  // every thread has the key before thread 0 clears it
+  if (key == 0) {
+    if (threadIdx.x == 0) st->done = 1;
+    return;
+  }
+  const u32 s = wtfdis::key_index(key);
+  for (u64 j = (u64)off[s] + threadIdx.x; j < off[s + 1]; j += DIS_BLOCK) atomicOr(&bitmap[ids[j] >> 5], 1u << (ids[j] & 31));
+  if (threadIdx.x == 0) {
+    const u32 k = st->kept;
+    out_index[k] = s;
+    out_gain[k] = wtfdis::key_gain(key);
+    st->kept = k + 1;
+    gain[s] = 0;
+    st->key = 0;
+  }
 }
 
 }  // namespace

@@ -195,6 +195,42 @@ class Engine:
     def minimize_feed_lanes(self, lanes, entry, op, indices):
         _chk(self.minimize_feed_lanes_rc(lanes, entry, op, indices), "minimize_feed_lanes")
 
+    # ---- the corpus distiller (csrc/engine_distill.h)
+    def distill_rc(self, n, offsets, values, eligible, want_out=True, want_counts=True):
+        """wtfgpu_distill's return code and outputs: (rc, index, gain, universe).
+        offsets / values / eligible None: a null pointer; want_out / want_counts
+        False: null output pointers."""
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+        val = None if values is None else np.ascontiguousarray(values, dtype=np.uint64)
+        el = None if eligible is None else np.ascontiguousarray(eligible, dtype=np.uint8)
+        oi, og = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        kept, uni = C.c_uint32(0), C.c_uint64(0)
+        p32, p64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        rc = self.L.wtfgpu_distill(self.ctx, n,
+                                   None if off is None else off.ctypes.data_as(p64),
+                                   None if val is None else val.ctypes.data_as(p64),
+                                   None if el is None else el.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                   oi.ctypes.data_as(p32) if want_out else None,
+                                   og.ctypes.data_as(p32) if want_out else None,
+                                   C.byref(kept) if want_counts else None, C.byref(uni) if want_counts else None)
+        k = kept.value
+        return rc, oi[:k].tolist(), og[:k].tolist(), uni.value
+
+    def distill(self, sets, eligible=None):
+        """The greedy cover of `sets` (each a strictly ascending sequence of
+        64-bit values, in rank order): (taken indices in the order taken, their
+        gains, the number of distinct values over the eligible sets)."""
+        sets = [np.ascontiguousarray(s, dtype=np.uint64) for s in sets]
+        off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        if sets:
+            off[1:] = np.cumsum([len(s) for s in sets], dtype=np.uint64)
+        val = np.concatenate(sets) if sets else np.zeros(0, dtype=np.uint64)
+        if len(val) == 0:
+            val = np.zeros(1, dtype=np.uint64)
+        rc, index, gain, universe = self.distill_rc(len(sets), off, val, eligible)
+        _chk(rc, "distill")
+        return index, gain, universe
+
     def read_whole_feed_lanes(self, lanes, stride=abi.FEED_STRIDE):
         """Each listed lane's whole feed (None: the lane has no feed)."""
         la = np.ascontiguousarray(lanes, dtype=np.uint32)

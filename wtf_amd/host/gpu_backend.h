@@ -132,6 +132,13 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   bool HasDeviceMinimizer() const override { return true; }
   bool SetDeviceMinimize(bool Feeds) override;
   bool DeviceMinimizeBase(const uint8_t *P, size_t N, uint32_t *Entry) override;
+  // `distill`: the cover runs in wtfgpu_distill; cov_ovf_warned_ is set once and never cleared
+  bool HasDeviceDistiller() const override { return true; }
+  int DeviceDistill(uint32_t N, const uint64_t *Offsets, const uint64_t *Values, const uint8_t *Eligible,
+                    uint32_t *OutIndex, uint32_t *OutGain, uint32_t *Kept, uint64_t *Universe) override {
+    return wtfgpu_distill(ctx_, N, Offsets, Values, Eligible, OutIndex, OutGain, Kept, Universe);
+  }
+  bool CoverageOverflowed() const override { return cov_ovf_warned_; }
   uint32_t FreeLanes() const override;
   bool StreamStep(const Target_t &Target, const std::vector<StreamTestcase_t> &In, uint64_t Slice,
                   std::vector<StreamResult_t> &Out, ModuleSlots *Slots, size_t *Taken) override;

@@ -10,6 +10,9 @@
 //   wtfgpu minimize --name hevd --target targets/hevd --input targets/hevd/crashes/crash-... [--output f]
 //       [--lanes 4096] [--limit l] [--rounds r]   (shrinks one crashing testcase, keeping its crash name;
 //       candidates made on the GPU, WTFGPU_MINIMIZE_HOST=1 uploads them instead: minimize.cc)
+//   wtfgpu distill --name tlv_server --target targets/tlv [--input targets/tlv/outputs] --output kept/
+//       [--results f] [--lanes 4096] [--limit l] [--edges] [--cov-set 8192]   (copies a covering subset of a
+//       corpus: greedy cover on the GPU, WTFGPU_DISTILL_HOST=1 runs it on the host instead: distill.cc)
 // The same runner drives the oracle twin (oracle/twin_backend.cc) for parity.
 #include <cstdio>
 #include <memory>

@@ -232,7 +232,7 @@ void PrintTestcaseRunStats(const LaneResult &L, size_t AggregateCoverage) {
 }
 
 bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
-  bool Minimize = false;
+  bool Minimize = false, Distill = false;
   int ModeWords = 0;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -245,6 +245,8 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     };
     if (a == "run" || a == "fuzz" || a == "master") O.mode = a, ModeWords++;
     else if (a == "minimize") Minimize = true;
+    else if (a == "distill") Distill = true;
+    else if (a == "--cov-set") O.cov_set = (uint32_t)strtoul(next("--cov-set"), nullptr, 0);
     else if (a == "--output") O.output = next("--output");
     else if (a == "--rounds") O.rounds = strtoull(next("--rounds"), nullptr, 0);
     else if (a == "--name") O.name = next("--name");
@@ -311,6 +313,22 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     }
     O.mode = "minimize";
   }
+  if (Distill) {
+    if (Minimize || ModeWords || !O.address.empty() || O.world > 1 || !O.module_so.empty()) {
+      fprintf(stderr, "distill is one in-process session: not with master (or another mode), --address, --world > 1 "
+                      "or --module-so\n");
+      return false;
+    }
+    if (O.output.empty()) {
+      fprintf(stderr, "distill needs --output <directory for the kept inputs>\n");
+      return false;
+    }
+    if (O.cov_set == 0) {
+      fprintf(stderr, "distill: --cov-set must be at least 1\n");
+      return false;
+    }
+    O.mode = "distill";
+  }
   if (O.mode == "master" && (O.address.empty() || O.nodes < 1)) {
     fprintf(stderr, "master needs --address and --nodes >= 1\n");
     return false;
@@ -334,13 +352,14 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     }
   }
   if (O.name.empty() || O.target.empty()) {
-    fprintf(stderr, "usage: [run|fuzz|master|minimize] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
+    fprintf(stderr, "usage: [run|fuzz|master|minimize|distill] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
                     "       [--lanes n] [--overlay-pages k] [--spill-pages s [--spill-lane-max x]] [--runs n] [--seconds s] [--seed s] [--full-coverage]\n"
                     "       [--serial-mutation] [--slice-steps s] [--regroup-steps r] [--rank r --world n [--exchange host:port | --nccl-id-file f]]\n"
                     "       [--address tcp://ip:port|unix://path [--batched] [--nodes k]] [--edges] [--device-attrib] [--device-mutate]\n"
                     "       [--device-packets]\n"
                     "       [--trace-path dir [--trace-type rip|cov|tenet] [--trace-cap n] [--tenet-cap bytes]] [--module-so m.so] [--serial]\n"
-                    "       minimize: --input <crashing testcase> [--output f] [--lanes n] [--limit l] [--rounds r]\n");
+                    "       minimize: --input <crashing testcase> [--output f] [--lanes n] [--limit l] [--rounds r]\n"
+                    "       distill: [--input dir] --output <dir> [--results f] [--lanes n] [--limit l] [--edges] [--cov-set n]\n");
     return false;
   }
   return true;
@@ -363,6 +382,7 @@ bool LoadTarget(const RunnerOptions &O, Options_t &Opts, CpuState_t &State) {
   Opts.GpuSpillLaneMax = O.spill_lane_max;
   // (the streaming replay reads whole sets as well: see RunnerMain)
   if (O.full_coverage || (O.mode == "run" && O.stream_run)) Opts.GpuCoverageSet = 8192;
+  if (O.mode == "distill") Opts.GpuCoverageSet = O.cov_set;  // whole sets too, sized by --cov-set
   Opts.Fuzz.Seed = (uint32_t)O.seed;
   if (!LoadCpuStateFromJSON(State, Opts.CpuStatePath)) {
     printf("Failed to load the CPU state from %s\n", Opts.CpuStatePath.string().c_str());
@@ -646,6 +666,7 @@ int RunnerMain(const RunnerOptions &O, Executor_t &Exec, const Options_t &Opts, 
   }
 
   if (O.mode == "minimize") return MinimizeMain(O, Exec, *Target, Slots);
+  if (O.mode == "distill") return DistillMain(O, Exec, *Target, Slots);
 
   // ---- fuzz against a remote master (wire.h): the client loop
   if (!O.address.empty()) return NodeMain(O, Exec, *Target, Slots);

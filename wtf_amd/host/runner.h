@@ -143,6 +143,18 @@ class Executor_t {
   virtual bool HasDeviceMinimizer() const { return false; }
   virtual bool SetDeviceMinimize(bool /*Feeds*/) { return false; }
   virtual bool DeviceMinimizeBase(const uint8_t *, size_t, uint32_t * /*Entry*/) { return false; }
+  // `distill`: true = this executor runs the greedy cover of
+  // csrc/engine_distill.h itself (DeviceDistill: wtfgpu_distill's arguments
+  // and return code); default: the session runs distill_host.
+  // CoverageOverflowed: some testcase's coverage set filled up since the
+  // executor was made, so a set it reported is incomplete.
+  virtual bool HasDeviceDistiller() const { return false; }
+  virtual int DeviceDistill(uint32_t /*N*/, const uint64_t * /*Offsets*/, const uint64_t * /*Values*/,
+                            const uint8_t * /*Eligible*/, uint32_t * /*OutIndex*/, uint32_t * /*OutGain*/,
+                            uint32_t * /*Kept*/, uint64_t * /*Universe*/) {
+    return -1;
+  }
+  virtual bool CoverageOverflowed() const { return false; }
   // Which ordered results the session wants bytes for (KeepsTestcase over its
   // own state): an executor that mutates on the device reads back only those
   // and sets StreamResult_t::has_tc on them. Called during StreamStep, on any
@@ -265,12 +277,14 @@ class CoverageExchange_t {
 void PrintTestcaseRunStats(const LaneResult &L, size_t AggregateCoverage);
 
 struct RunnerOptions {
-  std::string mode = "run";  // run | fuzz | master | minimize
+  std::string mode = "run";  // run | fuzz | master | minimize | distill
   std::string name;          // target name
   std::string target;        // dir with state/, inputs/, outputs/, crashes/
   std::string input;         // run: file or directory (default <target>/inputs)
   std::string results;       // run: JSON-lines output path
-  std::string output;        // minimize: where the minimised testcase goes (default <input>.min)
+  std::string output;        // minimize: where the minimised testcase goes (default <input>.min);
+                             // distill: the directory the kept inputs are copied into
+  uint32_t cov_set = 8192;   // distill: --cov-set, a lane's coverage set entries (Options_t::GpuCoverageSet)
   uint64_t rounds = 4096;    // minimize: the session stops after this many rounds
   uint64_t limit = 0;
   uint32_t lanes = 1;
@@ -552,6 +566,11 @@ class FuzzSession {
 // crash name, with the candidate stream of csrc/engine_minimize.h; candidates
 // are made on the device where the executor can. Returns the exit code.
 int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, ModuleSlots &Slots);
+// `distill` (distill.cc): replays the inputs for their whole coverage sets and
+// copies a covering subset, chosen by the greedy cover of
+// csrc/engine_distill.h, into O.output; the cover runs on the device where the
+// executor can. Returns the exit code.
+int DistillMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, ModuleSlots &Slots);
 
 bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O);
 // A Tenet entry stream (include/wtfgpu.h wtfgpu_set_tenet) as the reference's
