@@ -474,6 +474,24 @@ int wtfgpu_read_feeds_packed(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n,
  * result included). */
 int wtfgpu_collect_coverage_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t *out_lanes,
                                   uint64_t *out_rips, uint64_t cap, uint64_t *total, uint32_t *overflow);
+/* Keeping coverage (csrc/engine_covkeep.h defines the rule): does a lane's
+ * whole coverage set still hold a target set T?
+ * wtfgpu_coverage_target keeps a device copy of values[0, n) (opaque 64-bit
+ * values: rips, --edges values; each counted once a listing) that replaces any
+ * earlier copy; n == 0 is the empty target. It waits for every queue, and the
+ * copy is freed with the context. WTFGPU_ERR_INVALID for a null pointer with
+ * n > 0 or n >= 2^32.
+ * wtfgpu_coverage_contains fills, for each listed lane, missing[i] = how many
+ * of the target's values the lane's set lacks (the exact count), size[i] =
+ * the set's live entries and overflow[i] = 1 when the set filled up (0
+ * otherwise). It waits for the current queue, reads the sets and does not
+ * empty them (wtfgpu_clear_coverage_lanes does), so two calls in a row give
+ * the same answer. Before anything is queued: WTFGPU_ERR_INVALID for a null
+ * pointer with n > 0 or a lane outside the context; WTFGPU_ERR_STATE for a
+ * context without lanes, with coverage off or with no target set. */
+int wtfgpu_coverage_target(wtfgpu_ctx *ctx, const uint64_t *values, uint64_t n);
+int wtfgpu_coverage_contains(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t *missing, uint32_t *size,
+                             uint32_t *overflow);
 
 /* Bulk register I/O for lanes [first, first+count). */
 int wtfgpu_read_regs(wtfgpu_ctx *ctx, uint32_t first, uint32_t count, wtfgpu_regs_t *out);

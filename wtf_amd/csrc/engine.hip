@@ -96,6 +96,9 @@ struct wtfgpu_ctx {
   u64 *d_extra = nullptr;     // coverage values outside code pages (Dev::extra_keys)
   u8 *d_attr = nullptr;       // wtfgpu_attribute_coverage's candidates, owner table and result
   u64 attr_bytes = 0;
+  u64 *d_covtarget = nullptr;  // wtfgpu_coverage_target's copy (both queues read it)
+  u32 covtarget_n = 0;
+  bool covtarget_set = false;
   u8 *d_tn_buf = nullptr;     // Tenet traces (g_tn)
   u64 *d_tn_pos = nullptr, *d_tn_cpos = nullptr, *d_tn_ipos = nullptr, *d_tn_last = nullptr;
   u32 *d_tn_mute = nullptr;
@@ -658,6 +661,7 @@ int wtfgpu_destroy(wtfgpu_ctx *c) {
     if (q.stream) (void)hipStreamSynchronize(q.stream);
   free_lanes(c);
   dfree(c->d_attr);
+  dfree(c->d_covtarget);
   dfree(c->d_guc);
   if (c->d_warm) (void)hipFree(c->d_warm);
   dfree(c->d_pool);
@@ -2252,6 +2256,46 @@ int wtfgpu_collect_coverage_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t
   if (!c->d_covrip || n == 0) return WTFGPU_OK;
   if (!lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;
   return collect_sets(c, lanes, 0, n, out_lanes, out_rips, cap, total, overflow, 1);
+}
+
+// The target set of wtfgpu_coverage_contains (engine_covkeep.h): a device copy
+// that replaces the earlier one. Rare (once a session): every queue is drained
+// first, since a check in flight on either reads the copy it replaces.
+int wtfgpu_coverage_target(wtfgpu_ctx *c, const uint64_t *values, uint64_t n) {
+  if (!c || (n && !values) || n > 0xFFFFFFFFull) return WTFGPU_ERR_INVALID;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());
+  dfree(c->d_covtarget);
+  c->covtarget_n = 0;
+  c->covtarget_set = false;
+  if (dalloc(&c->d_covtarget, std::max<u64>(n, 1))) return WTFGPU_ERR_OOM;
+  if (n) HIPCHK(hipMemcpy(c->d_covtarget, values, n * 8, hipMemcpyHostToDevice));
+  c->covtarget_n = (u32)n;
+  c->covtarget_set = true;
+  return WTFGPU_OK;
+}
+
+// How much of the target each listed lane's set lacks (k_cov_contains); the
+// sets stay as they are.
+int wtfgpu_coverage_contains(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32_t *missing, uint32_t *size,
+                             uint32_t *overflow) {
+  if (!c || (n && (!lanes || !missing || !size || !overflow))) return WTFGPU_ERR_INVALID;
+  if (!c->d_gpr || !c->d_covrip || !c->covtarget_set) return WTFGPU_ERR_STATE;
+  if (!lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;
+  if (n == 0) return WTFGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  Side out = side_room((u64)n * 12);  // missing[n] | size[n] | overflow[n]
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, &out, 1)) return rc;
+  u8 *const S = c->q->d_scratch;
+  u32 *const o = (u32 *)(S + out.off);
+  k_cov_contains<<<(n + 3) / 4, 256, 0, c->q->stream>>>(c->P, (const u32 *)S, n, c->d_covtarget, c->covtarget_n, o,
+                                                        o + n, o + 2 * (u64)n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(missing, o, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipMemcpyAsync(size, o + n, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipMemcpyAsync(overflow, o + 2 * (u64)n, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
+  return WTFGPU_OK;
 }
 
 // The new values of a lane list attributed in list order on the device (see

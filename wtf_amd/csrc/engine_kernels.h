@@ -8,6 +8,7 @@
 #include "engine_mutate_packets.h"
 #include "engine_minimize.h"
 #include "engine_distill.h"
+#include "engine_covkeep.h"
 #include "engine_feedpack.h"
 
 namespace {
@@ -934,6 +935,40 @@ __global__ void k_attr_emit(const u64 *vals, const u32 *pos, const u32 *flag, co
   if (j >= s || !flag[j]) return;
   out_pos[at[j]] = pos[j];
   out_vals[at[j]] = vals[j];
+}
+
+// ---- keeping coverage (wtfgpu_coverage_contains; engine_covkeep.h defines the rule)
+// For position i of the list: how many of the target's nt values lane
+// lanes[i]'s set lacks, the set's live entries and its overflow flag. One wave
+// per position, four a block; the lane, its generation and its entry count are
+// the wave's. The wave strides over the target 64 values a step, each thread
+// probing the lane's table for its value (engine_covkeep.h's probe, as
+// log_value inserts); the ballot of "absent" is the step's count, the same in
+// every thread. The count is exact (no early exit). An empty set (cov_cnt 0)
+// costs one load: everything is missing. It reads the sets and changes
+// nothing; the caller checked the list and the target.
+__global__ __launch_bounds__(256) void k_cov_contains(Dev P, const u32 *lanes, u32 n, const u64 *target, u32 nt,
+                                                      u32 *missing, u32 *size, u32 *overflow) {
+  const u32 i = rfl32(blockIdx.x * 4 + (threadIdx.x >> 6)), lid = threadIdx.x & 63;
+  if (i >= n) return;
+  const u32 lane = rfl32(lanes[i]);
+  const u32 cnt = rfl32(P.cov_cnt[lane]);
+  u32 miss = nt;
+  if (cnt) {
+    const u32 g = rfl32(P.lane_gen[lane]), H = P.H;
+    const u64 *rip = P.cov_rip + (u64)lane * H;
+    const u32 *gen = P.cov_gen + (u64)lane * H;
+    miss = 0;
+    for (u32 t0 = 0; t0 < nt; t0 += 64) {
+      const u32 t = t0 + lid;
+      const bool absent = t < nt && !wtfkeep::table_has(rip, gen, H, g, target[t]);
+      miss += (u32)__popcll(__ballot(absent));
+    }
+  }
+  if (lid) return;
+  missing[i] = miss;
+  size[i] = cnt;
+  overflow[i] = P.cov_overflow[lane] ? 1u : 0u;
 }
 
 // ---- the corpus distiller (wtfgpu_distill; engine_distill.h defines the rule)

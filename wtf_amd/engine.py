@@ -231,6 +231,45 @@ class Engine:
         _chk(rc, "distill")
         return index, gain, universe
 
+    # ---- keeping coverage (csrc/engine_covkeep.h)
+    def coverage_target_rc(self, values) -> int:
+        """wtfgpu_coverage_target's return code. values None: a null pointer
+        (with n = 1); an empty sequence is the empty target."""
+        if values is None:
+            return self.L.wtfgpu_coverage_target(self.ctx, None, 1)
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        return self.L.wtfgpu_coverage_target(self.ctx, v.ctypes.data_as(C.POINTER(C.c_uint64)), len(v))
+
+    def coverage_target(self, values):
+        """The target set the following coverage_contains calls check against."""
+        _chk(self.coverage_target_rc(values), "coverage_target")
+
+    def coverage_contains_rc(self, lanes, want_out=True):
+        """wtfgpu_coverage_contains' return code and outputs: (rc, missing,
+        size, overflow), one entry a listed lane. lanes None: a null pointer
+        (with n = 1); want_out False: null output pointers."""
+        la = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.uint32)
+        n = 1 if la is None else len(la)
+        out = [np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3)]
+        p32 = C.POINTER(C.c_uint32)
+        ptrs = [o.ctypes.data_as(p32) if want_out else None for o in out]
+        rc = self.L.wtfgpu_coverage_contains(self.ctx, None if la is None else la.ctypes.data_as(p32), n, *ptrs)
+        return (rc, *[o[:n] for o in out])
+
+    def coverage_contains(self, lanes):
+        """For each listed lane: how many of the target's values its coverage
+        set lacks, the set's entries, and whether it overflowed (u32 arrays).
+        The sets are not emptied."""
+        rc, missing, size, overflow = self.coverage_contains_rc(lanes)
+        _chk(rc, "coverage_contains")
+        return missing, size, overflow
+
+    def clear_coverage_lanes(self, lanes):
+        """Empties the listed lanes' coverage sets (queued on the current queue)."""
+        la = np.ascontiguousarray(lanes, dtype=np.uint32)
+        _chk(self.L.wtfgpu_clear_coverage_lanes(self.ctx, la.ctypes.data_as(C.POINTER(C.c_uint32)), len(la)),
+             "clear_coverage_lanes")
+
     def read_whole_feed_lanes(self, lanes, stride=abi.FEED_STRIDE):
         """Each listed lane's whole feed (None: the lane has no feed)."""
         la = np.ascontiguousarray(lanes, dtype=np.uint32)

@@ -84,6 +84,7 @@ bool GpuBackend_t::Initialize(const Options_t &Opts, const CpuState_t &CpuState)
   nlanes_ = std::max<uint32_t>(Opts.GpuLanes, 1);
   overlay_pages_ = std::max<uint32_t>(Opts.GpuOverlayPages, 1);
   if (wtfgpu_alloc_lanes(ctx_, nlanes_, overlay_pages_, Opts.GpuCoverageSet)) return false;
+  cov_set_ = Opts.GpuCoverageSet;
   // the spill pool: the options, else the environment (the way a node gets it)
   uint64_t spill = Opts.GpuSpillPages;
   uint32_t spill_max = Opts.GpuSpillLaneMax;
@@ -1231,6 +1232,13 @@ bool GpuBackend_t::service_hits(const std::vector<uint32_t> &hits, uint32_t firs
 // (bochscpu_backend.cc:501-504); timed-out lanes have theirs revoked
 // (client.cc:122-125); the new rips join the device coverage map.
 void GpuBackend_t::finish_coverage(uint32_t n, std::vector<LaneResult> *out, std::vector<uint32_t> *timedout) {
+  if (cov_target_ && out) {  // verdicts instead of sets (check_coverage)
+    std::vector<uint32_t> all(n);
+    for (uint32_t l = 0; l < n; l++) all[l] = l;
+    last_new_coverage_.clear();
+    check_coverage(all.data(), n, *out);
+    return;
+  }
   if (device_attrib_ && !map_ahead_) {  // the same walk on the device (see attribute_on_device)
     std::vector<uint32_t> all(n);
     for (uint32_t l = 0; l < n; l++) all[l] = l;
@@ -1243,6 +1251,7 @@ void GpuBackend_t::finish_coverage(uint32_t n, std::vector<LaneResult> *out, std
       last_new_coverage_.clear();
       apply_attribution(all.data(), got, out, n == 1);
       if (full_coverage_) wtfgpu_reset_coverage(ctx_);  // parity mode: every lane ran against an empty map
+      if (of && out) mark_overflowed(all, *out);
       return;
     }
   }
@@ -1278,9 +1287,64 @@ void GpuBackend_t::finish_coverage(uint32_t n, std::vector<LaneResult> *out, std
   }
   if (full_coverage_) {  // parity mode: every lane ran against an empty map
     wtfgpu_reset_coverage(ctx_);
+    if (ovf && out) {
+      std::vector<uint32_t> all(n);
+      for (uint32_t l = 0; l < n; l++) all[l] = l;
+      mark_overflowed(all, *out);
+    }
     return;
   }
   commit_fresh(fresh);
+}
+
+// `minimize --keep-coverage` (csrc/engine_covkeep.h). The target goes to the
+// device once; full coverage stays on from then on, so nothing joins the
+// aggregate and every lane logs its whole set.
+bool GpuBackend_t::SetCoverageTarget(const uint64_t *Values, size_t N) {
+  if (!ctx_ || wtfgpu_coverage_target(ctx_, Values, N) != WTFGPU_OK) return false;
+  full_coverage_ = true;
+  cov_target_ = true;
+  cov_check_failed_ = false;
+  return true;
+}
+
+// The listed lanes' verdicts into their results, one call and 12 bytes a lane
+// back; their sets are emptied (the lanes get new testcases next). A call that
+// fails leaves no verdict (cov_missing ~0: nothing keeps) and fails the step.
+bool GpuBackend_t::check_coverage(const uint32_t *lanes, uint32_t n, std::vector<LaneResult> &res) {
+  const auto t0 = Clock::now();
+  if (keep_missing_.size() < n) {
+    keep_missing_.resize(n);
+    keep_size_.resize(n);
+    keep_ovf_.resize(n);
+  }
+  const bool ok = wtfgpu_coverage_contains(ctx_, lanes, n, keep_missing_.data(), keep_size_.data(),
+                                           keep_ovf_.data()) == WTFGPU_OK &&
+                  wtfgpu_clear_coverage_lanes(ctx_, lanes, n) == WTFGPU_OK;
+  for (uint32_t i = 0; i < n; i++) {
+    LaneResult &r = res[lanes[i]];
+    r.new_coverage.clear();
+    r.cov_missing = ok ? keep_missing_[i] : ~0u;
+    r.cov_size = ok ? keep_size_[i] : 0;
+    r.cov_overflow = ok && keep_ovf_[i] != 0;
+  }
+  if (!ok) {
+    cov_check_failed_ = true;
+    fprintf(stderr, "wtfgpu: the coverage check failed\n");
+  }
+  stats_.covlog_ms += ms_since(t0);
+  return ok;
+}
+
+// Whole sets read back in a call that reported an overflow: the sets that
+// filled up are among the ones holding all a table can (a set overflows only
+// at that count), and those are marked. Conservative by one case: a set that
+// reached the count exactly without dropping a value, read in the same call
+// as one that did drop.
+void GpuBackend_t::mark_overflowed(const std::vector<uint32_t> &lanes, std::vector<LaneResult> &res) {
+  const size_t cap = cov_set_ - cov_set_ / 4;
+  for (uint32_t l : lanes)
+    if (res[l].new_coverage.size() >= cap) res[l].cov_overflow = true;
 }
 
 // bochscpu_backend.cc:352-410: one testcase on lane 0; the caller already ran
@@ -1514,6 +1578,12 @@ void GpuBackend_t::apply_attribution(const uint32_t *lanes, uint64_t total, std:
 // device map. Their log bits are dropped (the lanes get new testcases next).
 void GpuBackend_t::collect_coverage(const std::vector<uint32_t> &lanes, std::vector<LaneResult> &res,
                                     const uint64_t *pf_hdr) {
+  if (cov_target_) {  // verdicts instead of sets: no reader below runs
+    last_new_coverage_.clear();
+    cov_sorted_.clear();
+    check_coverage(lanes.data(), (uint32_t)lanes.size(), res);
+    return;
+  }
   if (device_attrib_ && !map_ahead_ && !pf_hdr) {
     attr_rev_.resize(lanes.size());
     for (size_t i = 0; i < lanes.size(); i++) attr_rev_[i] = std::holds_alternative<Timedout_t>(res[lanes[i]].result);
@@ -1527,6 +1597,7 @@ void GpuBackend_t::collect_coverage(const std::vector<uint32_t> &lanes, std::vec
       cov_sorted_.resize(got);
       for (uint64_t k = 0; k < got; k++) cov_sorted_[k] = {lanes[attr_pos_[k]], attr_vals_[k]};
       if (!std::is_sorted(lanes.begin(), lanes.end())) std::sort(cov_sorted_.begin(), cov_sorted_.end());
+      if (of && full_coverage_) mark_overflowed(lanes, res);
       stats_.attrib_ms += ms_since(ta);
       return;
     }
@@ -1635,6 +1706,7 @@ void GpuBackend_t::collect_coverage(const std::vector<uint32_t> &lanes, std::vec
     }
   }
   commit_fresh(fresh);
+  if (ovf && full_coverage_) mark_overflowed(lanes, res);
   stats_.attrib_ms += ms_since(t1);
 }
 
@@ -1957,7 +2029,8 @@ bool GpuBackend_t::prefetch_part(Part &P) {
     return false;
   if (wtfgpu_prefetch_results(ctx_, P.lo, count, P.ex, P.nb, P.dc, args ? P.sargs : nullptr) != WTFGPU_OK)
     return false;
-  P.pf_cov = !full_coverage_ && !device_attrib_ && wtfgpu_prefetch_coverage(ctx_, P.lo, count, P.cov_hdr) == WTFGPU_OK;
+  P.pf_cov = !full_coverage_ && !device_attrib_ && !cov_target_ &&
+             wtfgpu_prefetch_coverage(ctx_, P.lo, count, P.cov_hdr) == WTFGPU_OK;
   return true;
 }
 
@@ -1985,6 +2058,9 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
     r.icount = 0;
     r.rip = 0;
     r.new_coverage.clear();
+    r.cov_missing = ~0u;
+    r.cov_size = 0;
+    r.cov_overflow = false;
   }, P.res_used.size() >= 8192);
   P.res_used.clear();
   const bool pf = P.pf;  // the exits (and counts, arguments, coverage count) are in P's pinned buffers
@@ -2015,6 +2091,9 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
   const size_t chunks = (n + kChunk - 1) / kChunk;
   if (hchunks_.size() < chunks) hchunks_.resize(chunks);
   const bool fill = !want_gprs_;
+  // with a coverage target every finished lane gets a LaneResult: the verdict
+  // goes into it (no counted nullptr results in that mode)
+  const bool counted = fill && !cov_target_;
   HostPool::Get().For(chunks, 1, [&](size_t c) {
     HarvestChunk &C = hchunks_[c];
     C.fin.clear();
@@ -2060,7 +2139,7 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
           if (touched_[l])
             v.result = Ok_t();
           else
-            plain = fill;
+            plain = counted;
           break;
         case WTFGPU_EXIT_FEED_FAULT: mark().handler_fault = true; break;  // U43: fill_lane makes it an engine error
         default:  // the engine cannot finish the testcase (see classify)
@@ -2159,6 +2238,7 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
   }
   stats_.bytes_ms += ms_since(tc);
   collect_coverage(finished, lres_, pf && P.pf_cov ? P.cov_hdr : nullptr);
+  if (cov_check_failed_) return false;
   {  // a plain lane that reported new coverage gets its LaneResult after all (entries sorted by lane)
     uint32_t last = ~0u;
     size_t added = 0;

@@ -139,6 +139,15 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
     return wtfgpu_distill(ctx_, N, Offsets, Values, Eligible, OutIndex, OutGain, Kept, Universe);
   }
   bool CoverageOverflowed() const override { return cov_ovf_warned_; }
+  // `minimize --keep-coverage`: while a target is set, the finished lanes' sets
+  // are checked where they are (wtfgpu_coverage_contains) and emptied; none of
+  // the set readers runs (the prefetch, --device-attrib's route, the plain
+  // collect), every finished lane gets a LaneResult with the verdict, and full
+  // coverage stays on: nothing joins the aggregate, so every lane logs its
+  // whole set
+  bool HasDeviceCoverageCheck() const override { return true; }
+  bool SetCoverageTarget(const uint64_t *Values, size_t N) override;
+  void ClearCoverageTarget() override { cov_target_ = false; }
   uint32_t FreeLanes() const override;
   bool StreamStep(const Target_t &Target, const std::vector<StreamTestcase_t> &In, uint64_t Slice,
                   std::vector<StreamResult_t> &Out, ModuleSlots *Slots, size_t *Taken) override;
@@ -319,6 +328,12 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   std::vector<uint8_t> cov_want_;  // lanes whose prefetched entries count (collect_coverage)
   std::vector<std::pair<uint32_t, uint64_t>> cov_sorted_;  // the same, sorted by (lane, rip)
   bool cov_ovf_warned_ = false;
+  bool cov_target_ = false;  // SetCoverageTarget: verdicts instead of sets
+  bool cov_check_failed_ = false;
+  uint32_t cov_set_ = 0;     // a lane's coverage set slots (Options_t::GpuCoverageSet)
+  std::vector<uint32_t> keep_missing_, keep_size_, keep_ovf_;  // wtfgpu_coverage_contains' answers
+  bool check_coverage(const uint32_t *lanes, uint32_t n, std::vector<LaneResult> &res);
+  void mark_overflowed(const std::vector<uint32_t> &lanes, std::vector<LaneResult> &res);
   bool want_gprs_ = true;
   uint64_t last_icount_ = 0;  // of the last Run
   LaneResult last_run_;       // the last Run's result and run stats (PrintRunStats)

@@ -18,11 +18,25 @@
 // round's base. REMOVE rounds run until one has no match, then ZERO rounds
 // likewise; so the result depends on the input and the target alone, not on
 // lane count, slice, lane order, queue or executor.
+//
+// --keep-coverage: the same session for an input that ends Ok_t, with another
+// match rule, the one of csrc/engine_covkeep.h. The input's own run happens
+// with full coverage; its whole set, sorted and unique, is the target T for
+// the whole session. A candidate matches iff it ends Ok_t without an engine
+// error, its set did not overflow and lacks none of T's values. An executor
+// with the device check (GpuBackend_t) is given T once and returns a verdict a
+// candidate, no set; every other executor (the oracle twin), and the gpu one
+// under WTFGPU_COVKEEP_HOST=1, stays in full coverage and the session counts
+// the missing values of each candidate's new_coverage with the header's host
+// function. A set of more than cap(--cov-set) values counts as overflowed
+// there, which is when a lane's table of --cov-set slots drops a value.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
+#include "../csrc/engine_covkeep.h"
 #include "../csrc/engine_minimize.h"
 #include "runner.h"
 
@@ -42,6 +56,17 @@ struct MinSession {
   uint32_t MaxPayload = 0;
   std::string W;  // the crash name to keep
 
+  // --keep-coverage: the target set instead of a crash name; the executor
+  // holds it and returns verdicts (CovOnDevice) or the session checks sets of
+  // at most CovCap values itself
+  bool KeepCov = false, CovOnDevice = false;
+  std::vector<uint64_t> T;
+  uint32_t CovCap = 0;
+  // candidates that ended Ok_t without an error but lacked a value of T, or
+  // whose set overflowed; coverage values handed to the session
+  uint64_t OkButMissing = 0, Overflowed = 0, ReadbackValues = 0;
+  std::vector<uint64_t> SetBuf;
+
   // the current base: its bytes (a feed's chunk bytes), its units, and for a
   // feed the indexed entry the stream reads (wtfpkt::entry_write)
   std::vector<uint8_t> Base, Entry;
@@ -58,10 +83,41 @@ struct MinSession {
   std::vector<uint64_t> Off, PrepOff;
   std::vector<PreparedInsert_t> Prep;
 
-  bool Matches(const LaneResult *L) const {
-    if (!L || L->error) return false;
-    const Crash_t *C = std::get_if<Crash_t>(&L->result);
-    return C && C->CrashName == W;
+  // *Values: the entries of the candidate's coverage set (--keep-coverage)
+  bool Matches(const LaneResult *L, uint32_t *Values) {
+    *Values = 0;
+    if (!KeepCov) {
+      if (!L || L->error) return false;
+      const Crash_t *C = std::get_if<Crash_t>(&L->result);
+      return C && C->CrashName == W;
+    }
+    if (L) ReadbackValues += L->new_coverage.size();
+    if (Literal) return false;  // the input's own run: MinimizeMain reads LiteralResult
+    // no LaneResult: the counted Ok_t without coverage, an empty set (an
+    // executor with a target set never returns it)
+    bool Ok = true, Error = false, Ovf = false;
+    uint64_t Missing = T.size();
+    if (L) {
+      Ok = std::holds_alternative<Ok_t>(L->result);
+      Error = L->error;
+      if (CovOnDevice) {
+        Missing = L->cov_missing;
+        Ovf = L->cov_overflow;
+        *Values = L->cov_size;
+      } else {
+        SetBuf = L->new_coverage;
+        std::sort(SetBuf.begin(), SetBuf.end());
+        SetBuf.erase(std::unique(SetBuf.begin(), SetBuf.end()), SetBuf.end());
+        Missing = wtfkeep::missing_sorted(SetBuf.data(), SetBuf.size(), T.data(), T.size());
+        Ovf = L->cov_overflow || SetBuf.size() > CovCap;
+        *Values = (uint32_t)SetBuf.size();
+      }
+    }
+    if (Ok && !Error) {
+      if (Ovf) Overflowed++;
+      else if (Missing) OkButMissing++;
+    }
+    return wtfkeep::keeps(Ok, Error, Ovf, Missing);
   }
 
   void SetBase(std::vector<uint8_t> B) {
@@ -151,10 +207,12 @@ struct MinSession {
     }
   }
 
-  // Runs the ordered candidates Idx; Match[i] = candidate Idx[i] keeps the crash
-  bool RunRound(const std::vector<uint64_t> &Idx, std::vector<uint8_t> &Match) {
+  // Runs the ordered candidates Idx; Match[i] = candidate Idx[i] keeps the
+  // crash (--keep-coverage: the coverage, and Values[i] = its set's entries)
+  bool RunRound(const std::vector<uint64_t> &Idx, std::vector<uint8_t> &Match, std::vector<uint32_t> &Values) {
     const size_t N = Idx.size();
     Match.assign(N, 0);
+    Values.assign(N, 0);
     std::vector<StreamTestcase_t> In;
     if (!Stream) {
       const size_t Lanes = std::max<uint32_t>(Exec.Lanes(), 1);
@@ -165,8 +223,9 @@ struct MinSession {
         Fill(Idx, b, e, In);
         Tc.clear();
         for (const StreamTestcase_t &T : In) Tc.emplace_back(T.data, T.size);
-        if (!Exec.RunBatch(Target, Tc, R, &Slots)) return false;
-        for (size_t i = b; i < e; i++) Match[i] = Matches(&R[i - b]);
+        if (KeepCov) Exec.ResetCoverage();  // whole sets: every batch runs against an empty aggregate
+        if (!Exec.RunBatch(Target, Tc, R, &Slots) || R.size() < e - b) return false;
+        for (size_t i = b; i < e; i++) Match[i] = Matches(&R[i - b], &Values[i]);
         if (Literal && !R.empty()) LiteralResult = R[0];
       }
       return true;
@@ -182,7 +241,7 @@ struct MinSession {
       Next += Taken;  // the rest is offered again
       for (const StreamResult_t &F : R) {
         if (F.tag >= N) return false;
-        Match[F.tag] = Matches(F.r);
+        Match[F.tag] = Matches(F.r, &Values[F.tag]);
         if (Literal) LiteralResult = F.r ? *F.r : LaneResult{};  // (no LaneResult: the common Ok_t)
         Got++;
       }
@@ -209,6 +268,8 @@ std::string JsonEscape(const std::string &S) {
 int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, ModuleSlots &Slots) {
   const auto T0 = std::chrono::steady_clock::now();
   MinSession S{O, Exec, Target, Slots};
+  S.KeepCov = O.keep_coverage;
+  S.CovCap = wtfkeep::cap(O.cov_set);
   // which stream the target gets
   const PacketMutator_t *M = Target.PacketMutator;
   const std::optional<InsertAction_t> &Ins = InsertAction_t::Declared();
@@ -246,11 +307,15 @@ int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, Mod
   if (S.Stream && Exec.TakesPrepared() && !Slots.Instances() && !getenv("WTF_NO_PREPARED_INSERT"))
     S.Prepare = Target.PrepareInsert;
 
+  // whole sets: the input's, and without the device check every candidate's
+  if (S.KeepCov) Exec.SetFullCoverage(true);
   // ---- the input, run once as it is: its crash name is the one to keep
+  // (--keep-coverage: its whole coverage set)
+  std::vector<uint8_t> Match;
+  std::vector<uint32_t> Values;
   {
-    std::vector<uint8_t> Match;
     S.Literal = &Input;
-    const bool Ran = S.RunRound(std::vector<uint64_t>{0}, Match);
+    const bool Ran = S.RunRound(std::vector<uint64_t>{0}, Match, Values);
     S.Literal = nullptr;
     if (!Ran) {
       printf("minimize: the executor failed\n");
@@ -258,12 +323,41 @@ int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, Mod
     }
     const LaneResult &R = S.LiteralResult;
     const Crash_t *C = std::get_if<Crash_t>(&R.result);
-    if (R.error || !C || C->CrashName.empty()) {
+    if (S.KeepCov) {
+      if (!R.error && C) {
+        printf("minimize: %s crashes (%s): drop --keep-coverage to minimise it by its crash name\n", O.input.c_str(),
+               C->CrashName.c_str());
+        return 1;
+      }
+      if (R.error || !std::holds_alternative<Ok_t>(R.result)) {
+        printf("minimize: %s does not end ok (%s): --keep-coverage minimises a testcase that does\n", O.input.c_str(),
+               R.error ? "engine error" : TestcaseResultName(R.result).c_str());
+        return 1;
+      }
+      S.T = R.new_coverage;
+      std::sort(S.T.begin(), S.T.end());
+      S.T.erase(std::unique(S.T.begin(), S.T.end()), S.T.end());
+      if (Exec.CoverageOverflowed() || R.cov_overflow || S.T.size() > S.CovCap) {
+        printf("minimize: the coverage set of %s filled up (a set of %u slots holds %u values), so the target would be "
+               "incomplete; raise --cov-set\n", O.input.c_str(), O.cov_set, S.CovCap);
+        return 1;
+      }
+    } else if (R.error || !C || C->CrashName.empty()) {
       printf("minimize: %s does not crash (%s): nothing to minimise\n", O.input.c_str(),
              R.error ? "engine error" : TestcaseResultName(R.result).c_str());
       return 1;
     }
-    S.W = C->CrashName;
+    if (!S.KeepCov) S.W = C->CrashName;
+  }
+  if (S.KeepCov) {
+    const char *CovEnv = getenv("WTFGPU_COVKEEP_HOST");
+    if (Exec.HasDeviceCoverageCheck() && !(CovEnv && atoi(CovEnv) == 1)) {
+      if (!Exec.SetCoverageTarget(S.T.data(), S.T.size())) {
+        printf("minimize: the executor refused the coverage target\n");
+        return 1;
+      }
+      S.CovOnDevice = true;
+    }
   }
   const char *HostEnv = getenv("WTFGPU_MINIMIZE_HOST");
   const bool HostOnly = HostEnv && atoi(HostEnv) != 0;
@@ -283,7 +377,7 @@ int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, Mod
   S.SetBase(std::move(First));
   std::vector<uint64_t> Idx;
   std::vector<uint32_t> Size, Cleared;
-  std::vector<uint8_t> Match;
+  uint64_t OutputValues = S.T.size();
   for (S.Op = wtfmin::kRemove; S.Op < (S.Feeds ? wtfmin::kZero : wtfmin::kNumOps);) {
     if (Rounds >= O.rounds) {
       StoppedByRounds = true;
@@ -315,7 +409,7 @@ int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, Mod
       }
       UploadBytes += S.Base.size();
     }
-    if (!S.RunRound(Idx, Match)) {
+    if (!S.RunRound(Idx, Match, Values)) {
       printf("minimize: the executor failed\n");
       return 1;
     }
@@ -328,6 +422,7 @@ int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, Mod
       S.Op++;
       continue;
     }
+    OutputValues = Values[Best];
     std::vector<uint8_t> Next;
     S.Candidate(Idx[Best], Next);
     S.SetBase(std::move(Next));
@@ -341,11 +436,18 @@ int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, Mod
     printf("minimize: could not write %s\n", OutPath.string().c_str());
     return 1;
   }
-  printf("{\"input_bytes\":%zu,\"output_bytes\":%zu,\"rounds\":%llu,\"remove_rounds\":%llu,\"zero_rounds\":%llu,"
-         "\"candidates\":%llu,\"skipped\":%llu,\"crash\":\"%s\",\"stopped_by_rounds\":%s,\"seconds\":%.3f,"
+  if (S.CovOnDevice) Exec.ClearCoverageTarget();
+  char Cov[256] = "";
+  if (S.KeepCov)
+    snprintf(Cov, sizeof(Cov), "\"values\":%zu,\"output_values\":%llu,\"cov_on_device\":%s,"
+             "\"cov_readback_values\":%llu,\"overflowed\":%llu,\"ok_but_missing\":%llu,", S.T.size(), (unsigned long long)OutputValues,
+             S.CovOnDevice ? "true" : "false", (unsigned long long)S.ReadbackValues, (unsigned long long)S.Overflowed,
+             (unsigned long long)S.OkButMissing);
+  printf("{\"mode\":\"%s\",%s\"input_bytes\":%zu,\"output_bytes\":%zu,\"rounds\":%llu,\"remove_rounds\":%llu,"
+         "\"zero_rounds\":%llu,\"candidates\":%llu,\"skipped\":%llu,\"crash\":\"%s\",\"stopped_by_rounds\":%s,\"seconds\":%.3f,"
          "\"on_device\":%s,\"upload_bytes\":%llu,\"executor\":%s}\n",
-         Input.size(), Out.size(), (unsigned long long)Rounds, (unsigned long long)RemoveRounds,
-         (unsigned long long)ZeroRounds, (unsigned long long)Candidates, (unsigned long long)SkippedN,
+         S.KeepCov ? "coverage" : "crash", Cov, Input.size(), Out.size(), (unsigned long long)Rounds,
+         (unsigned long long)RemoveRounds, (unsigned long long)ZeroRounds, (unsigned long long)Candidates, (unsigned long long)SkippedN,
          JsonEscape(S.W).c_str(), StoppedByRounds ? "true" : "false", SecondsSince(T0), S.OnDevice ? "true" : "false",
          (unsigned long long)UploadBytes, Exec.StatsJson().c_str());
   return 0;

@@ -249,6 +249,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     else if (a == "--cov-set") O.cov_set = (uint32_t)strtoul(next("--cov-set"), nullptr, 0);
     else if (a == "--output") O.output = next("--output");
     else if (a == "--rounds") O.rounds = strtoull(next("--rounds"), nullptr, 0);
+    else if (a == "--keep-coverage") O.keep_coverage = true;
     else if (a == "--name") O.name = next("--name");
     else if (a == "--target") O.target = next("--target");
     else if (a == "--input") O.input = next("--input");
@@ -301,6 +302,10 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     fprintf(stderr, "--rank must be in [0, --world)\n");
     return false;
   }
+  if (O.keep_coverage && (!Minimize || Distill)) {
+    fprintf(stderr, "--keep-coverage is for minimize\n");
+    return false;
+  }
   if (Minimize) {
     if (ModeWords || !O.address.empty() || O.world > 1 || !O.module_so.empty()) {
       fprintf(stderr, "minimize is one in-process session: not with master (or another mode), --address, --world > 1 "
@@ -309,6 +314,10 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     }
     if (O.input.empty()) {
       fprintf(stderr, "minimize needs --input <crashing testcase>\n");
+      return false;
+    }
+    if (O.keep_coverage && O.cov_set == 0) {
+      fprintf(stderr, "minimize: --cov-set must be at least 1\n");
       return false;
     }
     O.mode = "minimize";
@@ -359,6 +368,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
                     "       [--device-packets]\n"
                     "       [--trace-path dir [--trace-type rip|cov|tenet] [--trace-cap n] [--tenet-cap bytes]] [--module-so m.so] [--serial]\n"
                     "       minimize: --input <crashing testcase> [--output f] [--lanes n] [--limit l] [--rounds r]\n"
+                    "                 [--keep-coverage [--edges] [--cov-set n]] (--input: a testcase that ends ok)\n"
                     "       distill: [--input dir] --output <dir> [--results f] [--lanes n] [--limit l] [--edges] [--cov-set n]\n");
     return false;
   }
@@ -383,6 +393,7 @@ bool LoadTarget(const RunnerOptions &O, Options_t &Opts, CpuState_t &State) {
   // (the streaming replay reads whole sets as well: see RunnerMain)
   if (O.full_coverage || (O.mode == "run" && O.stream_run)) Opts.GpuCoverageSet = 8192;
   if (O.mode == "distill") Opts.GpuCoverageSet = O.cov_set;  // whole sets too, sized by --cov-set
+  if (O.mode == "minimize" && O.keep_coverage) Opts.GpuCoverageSet = O.cov_set;  // likewise
   Opts.Fuzz.Seed = (uint32_t)O.seed;
   if (!LoadCpuStateFromJSON(State, Opts.CpuStatePath)) {
     printf("Failed to load the CPU state from %s\n", Opts.CpuStatePath.string().c_str());

@@ -41,6 +41,14 @@ struct LaneResult {
   // (B_insn), dirty pages, RecordEdge calls and those new to the testcase's set
   uint64_t bytes = 0, edges = 0, edges_new = 0;
   uint32_t dirty = 0;
+  // `minimize --keep-coverage` on an executor with a coverage target set
+  // (SetCoverageTarget): the verdict of csrc/engine_covkeep.h instead of
+  // new_coverage. cov_missing = how many of the target's values the
+  // testcase's whole set lacks (~0: no verdict), cov_size = the set's
+  // entries. cov_overflow is also set without a target, by an executor that
+  // reports whole sets and knows this one filled up.
+  uint32_t cov_missing = ~0u, cov_size = 0;
+  bool cov_overflow = false;
 };
 
 struct StreamTestcase_t {
@@ -155,6 +163,17 @@ class Executor_t {
     return -1;
   }
   virtual bool CoverageOverflowed() const { return false; }
+  // `minimize --keep-coverage`: true = this executor answers "does the
+  // testcase's whole coverage set still hold the target" itself
+  // (csrc/engine_covkeep.h). While a target is set (sorted unique values;
+  // SetCoverageTarget false = it cannot), every finished testcase comes back
+  // with a LaneResult (never the counted nullptr of StreamResult_t) whose
+  // cov_missing / cov_size / cov_overflow are filled and whose new_coverage is
+  // empty: no set is read back. Default: the session checks
+  // new_coverage itself.
+  virtual bool HasDeviceCoverageCheck() const { return false; }
+  virtual bool SetCoverageTarget(const uint64_t * /*Values*/, size_t /*N*/) { return false; }
+  virtual void ClearCoverageTarget() {}
   // Which ordered results the session wants bytes for (KeepsTestcase over its
   // own state): an executor that mutates on the device reads back only those
   // and sets StreamResult_t::has_tc on them. Called during StreamStep, on any
@@ -284,8 +303,11 @@ struct RunnerOptions {
   std::string results;       // run: JSON-lines output path
   std::string output;        // minimize: where the minimised testcase goes (default <input>.min);
                              // distill: the directory the kept inputs are copied into
-  uint32_t cov_set = 8192;   // distill: --cov-set, a lane's coverage set entries (Options_t::GpuCoverageSet)
+  uint32_t cov_set = 8192;   // distill, minimize --keep-coverage: --cov-set, a lane's coverage set entries (Options_t::GpuCoverageSet)
   uint64_t rounds = 4096;    // minimize: the session stops after this many rounds
+  // minimize --keep-coverage: the input ends Ok_t and every value of its whole
+  // coverage set is kept (csrc/engine_covkeep.h) instead of a crash name
+  bool keep_coverage = false;
   uint64_t limit = 0;
   uint32_t lanes = 1;
   uint32_t overlay_pages = 32;
@@ -564,7 +586,10 @@ class FuzzSession {
 
 // `minimize` (minimize.cc): shrinks the crashing testcase O.input, keeping its
 // crash name, with the candidate stream of csrc/engine_minimize.h; candidates
-// are made on the device where the executor can. Returns the exit code.
+// are made on the device where the executor can. With O.keep_coverage the
+// input ends Ok_t instead and every candidate must still cover what it covered
+// (csrc/engine_covkeep.h), checked on the device where the executor can.
+// Returns the exit code.
 int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, ModuleSlots &Slots);
 // `distill` (distill.cc): replays the inputs for their whole coverage sets and
 // copies a covering subset, chosen by the greedy cover of
