@@ -220,6 +220,7 @@ int sim_run_full(const uint64_t *gpfns, const uint8_t *pages, uint64_t npages, c
     }
     int x;
     tn_insn_begin(L.lane);
+    L.keep = 0;
     for (int attempt = 0;; attempt++) {
       L.miss = 0;
       L.pend = 0;

@@ -168,6 +168,7 @@ void spill_sim_run(SpillSim *h, uint32_t lane, uint64_t rdi, uint64_t rcx, uint6
     }
     uint64_t next = 0;
     int x;
+    L.keep = 0;
     for (int attempt = 0;; attempt++) {
       L.miss = 0;
       L.pend = 0;

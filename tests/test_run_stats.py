@@ -8,7 +8,11 @@ coverage set). The per-testcase counters are also printed with every result
 ("bytes", "dirty", "edges", "edges_new") and must be the same on the GPU node
 and on the twin. Memory accesses count the engine's B_insn (instruction and
 data bytes); bochscpu's count of linear + physical accesses is unpinned
-(no bochscpu build)."""
+(no bochscpu build). An instruction that restarts after a TLB miss
+or a first write counts the attempt that retires; a rep string counts each
+finished iteration, and a gather that retires counts its instruction bytes
+once and every element it loaded, in whichever attempt (a gather that ends in
+a guest fault counts nothing: U46; tests/test_page_edge.py)."""
 import os
 import re
 import subprocess

@@ -101,6 +101,31 @@ def test_check_sees_every_field_it_claims_to_compare(fam):
     assert exercised == want, want - exercised
 
 
+@pytest.mark.parametrize("fam", V.PLACED, ids=[f.name for f in V.PLACED])
+def test_judge_sees_the_byte_count_of_a_placed_case(fam):
+    """A placed replay (tests/test_page_edge.py) compares one more field, the
+    executor's byte count with the oracle's for the same placed case: under
+    every rule a placement is judged by, a perturbed nbytes must be reported,
+    and what check() reports at the original place judge() reports here."""
+    rules = set()
+    for kind in V.KINDS:
+        cases, seen = [], set()
+        for c in V.placed_cases(fam, kind):
+            key = (c.get("name", c["code"]).split(".")[0], c["at"].rule)
+            if key not in seen and len(seen) < 32:
+                seen.add(key)
+                cases.append(c)
+        for c, o in zip(cases, V.replay_oracle(fam, cases), strict=True):
+            assert "bytes" in fam.fields_of(c) and "bytes" not in fam.fields
+            assert V.judge(fam, c, o, o) is None
+            bad = V.judge(fam, c, dataclasses.replace(o, nbytes=o.nbytes + 1), o)
+            assert bad is not None and "bytes" in bad[0], (c.get("name"), c["code"], kind, bad)
+            if c["at"].rule == "native" and "trap_mx" not in c:
+                assert V.judge(fam, c, dataclasses.replace(o, icount=o.icount + 1), o) is not None
+            rules.add(c["at"].rule)
+    assert {"native", "fault"} <= rules
+
+
 def test_the_binding_matches_the_library():
     L = simlane.lib()   # asserts ctypes.sizeof(SimResult) == sim_result_size()
     assert L.sim_result_size() == simlane.C.sizeof(simlane.SimResult)

@@ -18,6 +18,7 @@ struct Lane {
   u64 miss_va;               // pending translation (TLB miss or copy-on-write)
   u32 tnext, ovn, cpl, status, lane, exvec, exerr, exop;
   u32 miss, miss_acc, flush, pend;  // pend: bytes accessed by the attempt in flight
+  u32 keep;                         // bytes of the gather elements the instruction's attempts finished for good
   u32 nodeliver;                    // this fault could not be delivered through the guest IDT
   u32 cgen, ccnt;                   // coverage set: generation, live entries
   u32 simd;                         // bit 0: SSE usable, bit 1: AVX usable, bit 2: AVX-512 state on (simd_bits)

@@ -123,7 +123,7 @@ __device__ __forceinline__ void lane_min_load(const Dev &P, u32 lane, Lane &L) {
   L.nbytes = 0;
   tlb_flush(L);
   L.tnext = 0;
-  L.miss = L.miss_acc = L.flush = L.pend = 0;
+  L.miss = L.miss_acc = L.flush = L.pend = L.keep = 0;
   L.nodeliver = 0;
 }
 

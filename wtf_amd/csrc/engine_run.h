@@ -129,7 +129,7 @@ __device__ __forceinline__ void load_lane(const Dev &P, u32 lane, Lane &L) {
   }
   L.exvec = L.exerr = L.exop = 0;
   L.exaddr = 0;
-  L.miss = L.miss_acc = L.flush = L.pend = 0;
+  L.miss = L.miss_acc = L.flush = L.pend = L.keep = 0;
   L.nodeliver = 0;
   L.miss_va = 0;
 }
@@ -587,6 +587,7 @@ __device__ __noinline__ int exec_generic(const Dev &P, Lane &L, const UOp *ul, u
 __device__ __noinline__ int exec_retry(const Dev &P, Lane &L, const UOp *ul, u64 &next) {
   int x;
   tn_insn_begin(L.lane);
+  L.keep = 0;
   for (int attempt = 0;; attempt++) {
     L.miss = 0;
     L.pend = 0;
@@ -958,6 +959,7 @@ __device__ __noinline__ void slow_step(const Dev &P, Lane &L, u64 grip, u64 lptr
     u64 next = 0;
     int x;
     tn_insn_begin(L.lane);
+    L.keep = 0;
     for (int attempt = 0;; attempt++) {
       L.miss = 0;
       L.pend = 0;
