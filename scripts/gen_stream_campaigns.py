@@ -42,6 +42,12 @@ CONFIGS = [
      "limit": 10000000, "max_len": 1028, "extra": [], "env": {}},
     {"id": "hevd_bare_16384", "target": "hevd", "name": "hevd", "lanes": 16384, "runs": 32768,
      "limit": 10000000, "max_len": 1028, "extra": [], "env": {}},
+    # the one-part path (no pipelining: the harvest runs in the refill's call
+    # and reads the exits, counts and StopWithArgs arguments itself)
+    {"id": "tlv_256_short_slices_one_part", "target": "tlv", "name": "tlv_server", "lanes": 256, "runs": 8192,
+     "limit": 100000, "max_len": 0x1000, "extra": _SHORT, "env": {"WTFGPU_STREAM_PARTS": "1"}},
+    {"id": "hevd_bare_256_one_part", "target": "hevd", "name": "hevd", "lanes": 256, "runs": 32768,
+     "limit": 10000000, "max_len": 1028, "extra": [], "env": {"WTFGPU_STREAM_PARTS": "1"}},
 ]
 
 _BUILD = {"tlv": H.build_target, "hevd": H.build_hevd_target}

@@ -16,13 +16,19 @@ Configs (a few seconds each):
   * tlv, 16,384 lanes, default slice: halves of 8,192 lanes cross every
     "parallel above N lanes" threshold;
   * the bare HEVD look-alike at 256 and 16,384 lanes: host handlers,
-    StopWithArgs naming, handler-fault engine errors.
+    StopWithArgs naming, handler-fault engine errors;
+  * the first and the fourth again with WTFGPU_STREAM_PARTS=1: one part, not
+    pipelined, so the harvest runs in the refill's call and reads the exits,
+    byte and dirty counts and StopWithArgs arguments itself.
 
 Every recorded key must match. The recording build ran each config twice:
-the tlv configs agreed with themselves on every key; both HEVD configs
-differed from themselves in the kernel's group_steps alone (885592 / 885566
-and 619582 / 619589), so the fixture lists that key as unstable for them and
-holds them to every other key (counts, crash names, corpus entries).
+the tlv configs agreed with themselves on every key; the HEVD configs
+differed from themselves in the kernel's group_steps alone (885592 / 885566,
+619582 / 619589 and, one part, 941267 / 941266), so the fixture lists that key
+as unstable for them and holds them to every other key (counts, crash names,
+corpus entries). The two one-part records were added later, recorded with the
+other five again (which came out unchanged) from the commit before the
+streaming step was split into named phases.
 """
 import importlib.util
 import json
@@ -42,7 +48,8 @@ _spec.loader.exec_module(G)
 with open(os.path.join(H.ROOT, "tests", "golden", "stream_campaigns.json")) as _f:
     FIXTURE = {c["config"]["id"]: c for c in json.load(_f)["configs"]}
 
-IDS = ("tlv_256_short_slices", "tlv_256_short_slices_host_bp", "tlv_16384", "hevd_bare_256", "hevd_bare_16384")
+IDS = ("tlv_256_short_slices", "tlv_256_short_slices_host_bp", "tlv_16384", "hevd_bare_256", "hevd_bare_16384",
+       "tlv_256_short_slices_one_part", "hevd_bare_256_one_part")
 
 
 def test_fixture_holds_every_config():

@@ -20,6 +20,9 @@ thread_local bool GpuBackend_t::scouting_ = false;
 
 namespace {
 constexpr uint64_t kFeedRegion = 16384;  // engine.hip wtfgpu_set_feed_lanes per-lane region
+constexpr size_t kRefillChunk = 1024, kHarvestChunk = 2048;  // lanes per loop index of the streaming passes
+// B_exec = instruction + data bytes, 2 x 4096 per dirty page, testcase bytes
+constexpr uint64_t b_exec(uint64_t nb, uint32_t dirty, uint64_t tc) { return nb + 2ull * 4096 * dirty + tc; }
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
@@ -59,6 +62,21 @@ GpuBackend_t::~GpuBackend_t() {
       if (p) wtfgpu_host_free(ctx_, p);
   if (wpin_) wtfgpu_host_free(ctx_, wpin_);
   if (ctx_) wtfgpu_destroy(ctx_);
+}
+
+// Makes the pinned buffer `p` of `cap` bytes hold `need`: when it does not, it
+// is freed and allocated anew with `grow` bytes (at least `need`).
+template <class T>
+bool GpuBackend_t::fit_pinned(T *&p, uint64_t &cap, uint64_t need, uint64_t grow) {
+  if (need <= cap) return true;
+  if (p) wtfgpu_host_free(ctx_, p);
+  p = nullptr;
+  cap = 0;
+  void *q = nullptr;
+  if (wtfgpu_host_alloc(ctx_, grow, &q)) return false;
+  p = (T *)q;
+  cap = grow;
+  return true;
 }
 
 bool GpuBackend_t::LoadDump(const std::string &dump_path) { return dump_.Parse(dump_path); }
@@ -744,14 +762,7 @@ int GpuBackend_t::flush_lanes(const std::vector<uint32_t> &lanes) {
     }
   std::vector<wtfgpu_write_t> writes(roff[nl] + crecs);
   const uint64_t total = boff[nl] + cbytes;
-  if (total > wpin_cap_) {
-    if (wpin_) wtfgpu_host_free(ctx_, wpin_);
-    wpin_ = nullptr;
-    wpin_cap_ = std::max<uint64_t>(total * 2, 1 << 20);
-    void *p = nullptr;
-    if (wtfgpu_host_alloc(ctx_, wpin_cap_, &p)) return WTFGPU_ERR_OOM;
-    wpin_ = (uint8_t *)p;
-  }
+  if (!fit_pinned(wpin_, wpin_cap_, total, std::max<uint64_t>(total * 2, 1 << 20))) return WTFGPU_ERR_OOM;
   HostPool::Get().For(nl, 256, [&](size_t i) {
     const uint32_t l = lanes[i];
     LaneView &v = view(l);
@@ -804,60 +815,74 @@ int GpuBackend_t::flush_lanes(const std::vector<uint32_t> &lanes) {
 bool GpuBackend_t::classify(const std::vector<uint32_t> &pending, uint32_t first, const wtfgpu_exit_t *ex,
                             std::vector<uint8_t> &done, std::vector<LaneResult> *out, std::vector<uint32_t> &hits,
                             const uint64_t *stop_args) {
-  std::vector<uint8_t> hit(pending.size(), 0);
+  std::vector<uint8_t> kind(pending.size(), ExitClass::Finished);
   HostPool::Get().For(pending.size(), 1024, [&](size_t pi) {
     const uint32_t l = pending[pi];
     if (done[l - first]) return;
-    const wtfgpu_exit_t &e = ex[l - first];
-    // a view the host has not touched since its reset holds no result: the
-    // common exits (Stop(Ok), still running, a breakpoint) leave it so
-    LaneView &v = views_[l];
-    const auto mark = [&]() -> LaneView & {
-      touched_[l] = 1;
-      return v;
-    };
-    switch (e.status) {
-      case WTFGPU_EXIT_BREAKPOINT: hit[pi] = 1; return;
-      case WTFGPU_RUNNING: return;  // sliced: still running when the slice ended
-      case WTFGPU_EXIT_TIMEOUT: mark().result = Timedout_t(); break;  // bochscpu_backend.cc:458-469
-      case WTFGPU_EXIT_INT3:                                           // :595-619
-      case WTFGPU_EXIT_HLT: mark().result = Crash_t(); break;          // :690-697
-      case WTFGPU_EXIT_CR3: mark().result = Cr3Change_t(); break;      // :628-657
-      case WTFGPU_EXIT_FAULT: mark().result = FaultToResult(e.vector, e.error, e.rip, e.addr, e.opcode); break;
-      case WTFGPU_EXIT_STOPPED: break;
-      case WTFGPU_EXIT_STOP_OK:  // device Feed action: Stop(Ok_t()) (an untouched view reads as Ok already)
-        if (touched_[l]) v.result = Ok_t();
-        break;
-      case WTFGPU_EXIT_STOP_ARGS: hit[pi] = 2; return;                  // named below from the kept arguments
-      case WTFGPU_EXIT_FEED_FAULT: mark().handler_fault = true; break;  // U43: fill_results makes it an engine error
-      default:
-        // unimplemented opcode / overlay full / a device Feed write that
-        // failed: the engine cannot finish the testcase. Not a target bug:
-        // flagged as an engine error, with an unnamed Crash_t (which no
-        // master saves, server.h:861-877) as its result
-        if (out) (*out)[l].error = true;
-        if (!v.result) mark().result = Crash_t();
-        if (e.status == WTFGPU_EXIT_UNIMPLEMENTED) {
-          stats_.err_unimpl++;
-          stats_.unimpl_ops.add(e.opcode);
-          stats_.last_unimpl_op = e.opcode;
-          stats_.last_unimpl_rip = e.rip;
-        } else if (e.status == WTFGPU_EXIT_OVERLAY_FULL) {
-          stats_.err_overlay++;
-        } else {
-          stats_.err_other++;
-        }
-        break;
-    }
-    done[l - first] = 1;
+    kind[pi] = classify_exit(l, ex[l - first], out ? &(*out)[l] : nullptr, false).kind;
+    if (kind[pi] == ExitClass::Finished) done[l - first] = 1;
   }, pending.size() >= 2048);
-  std::vector<uint32_t> named;
+  std::vector<uint32_t> named;  // named below from the kept arguments
   for (size_t pi = 0; pi < pending.size(); pi++) {
-    if (hit[pi] == 1) hits.push_back(pending[pi]);
-    if (hit[pi] == 2) named.push_back(pending[pi]);
+    if (kind[pi] == ExitClass::Hit) hits.push_back(pending[pi]);
+    if (kind[pi] == ExitClass::Named) named.push_back(pending[pi]);
   }
   name_stop_args(named, first, ex, done, out, stop_args);
   return true;
+}
+
+// One lane's exit. A view the host has not touched since its reset holds no
+// result: the common exits (Stop(Ok), still running, a breakpoint) leave it
+// so. A result the exit alone decides goes through the view, or with
+// direct_ok, on a view the host never touched, straight into *r (the view
+// stays untouched, so the refill has nothing to reset).
+GpuBackend_t::ExitClass GpuBackend_t::classify_exit(uint32_t l, const wtfgpu_exit_t &e, LaneResult *r,
+                                                    bool direct_ok) {
+  ExitClass c{ExitClass::Finished};
+  LaneView &v = views_[l];
+  const auto ends = [&](TestcaseResult_t &&R) {
+    if (direct_ok && !touched_[l]) {
+      r->result = std::move(R);
+      c.direct = true;
+    } else {
+      view(l).result = std::move(R);
+    }
+  };
+  switch (e.status) {
+    case WTFGPU_EXIT_BREAKPOINT: c.kind = ExitClass::Hit; break;
+    case WTFGPU_RUNNING: c.kind = ExitClass::Running; break;  // sliced: still running when the slice ended
+    case WTFGPU_EXIT_STOP_ARGS: c.kind = ExitClass::Named; break;
+    case WTFGPU_EXIT_TIMEOUT: ends(Timedout_t()); break;  // bochscpu_backend.cc:458-469
+    case WTFGPU_EXIT_INT3:                                 // :595-619
+    case WTFGPU_EXIT_HLT: ends(Crash_t()); break;          // :690-697
+    case WTFGPU_EXIT_CR3: ends(Cr3Change_t()); break;      // :628-657
+    case WTFGPU_EXIT_FAULT: ends(FaultToResult(e.vector, e.error, e.rip, e.addr, e.opcode)); break;
+    case WTFGPU_EXIT_STOPPED: break;
+    case WTFGPU_EXIT_STOP_OK:  // device Feed action: Stop(Ok_t()) (an untouched view reads as Ok already)
+      c.ok = !touched_[l];
+      if (!c.ok) v.result = Ok_t();
+      break;
+    case WTFGPU_EXIT_FEED_FAULT: view(l).handler_fault = true; break;  // U43: fill_lane makes it an engine error
+    default:
+      // unimplemented opcode / overlay full / a device Feed write that
+      // failed: the engine cannot finish the testcase. Not a target bug:
+      // flagged as an engine error, with an unnamed Crash_t (which no
+      // master saves, server.h:861-877) as its result
+      if (r) r->error = true;
+      if (!v.result) view(l).result = Crash_t();
+      if (e.status == WTFGPU_EXIT_UNIMPLEMENTED) {
+        stats_.err_unimpl++;
+        stats_.unimpl_ops.add(e.opcode);
+        stats_.last_unimpl_op = e.opcode;
+        stats_.last_unimpl_rip = e.rip;
+      } else if (e.status == WTFGPU_EXIT_OVERLAY_FULL) {
+        stats_.err_overlay++;
+      } else {
+        stats_.err_other++;
+      }
+      break;
+  }
+  return c;
 }
 
 // Device StopWithArgs actions: the handler's Stop(Result(GetArg(0..5))) for
@@ -905,10 +930,10 @@ bool GpuBackend_t::fill_results(const std::vector<uint32_t> &lanes, uint32_t fir
   return !out || fill_lanes(fin, first, ex, *out);
 }
 
-void GpuBackend_t::fill_lane(uint32_t l, const wtfgpu_exit_t &e, LaneResult &r) {
+void GpuBackend_t::fill_lane(uint32_t l, const wtfgpu_exit_t &e, LaneResult &r, bool direct) {
   const LaneView &v = views_[l];  // untouched since its reset: no result, no fault
   const bool t = touched_[l] != 0;
-  r.result = t && v.result ? std::move(*v.result) : TestcaseResult_t(Ok_t());  // the view is reset at refill
+  if (!direct) r.result = t && v.result ? std::move(*v.result) : TestcaseResult_t(Ok_t());  // (reset at refill)
   if (t && v.handler_fault) {  // U43: an engine error, never a named crash
     r.result = Crash_t();
     r.error = true;
@@ -1429,7 +1454,7 @@ bool GpuBackend_t::RunBatch(const Target_t &Target, const std::vector<std::pair<
     std::vector<uint32_t> dc(n);
     if (wtfgpu_read_bytes(ctx_, 0, n, nb.data()) == WTFGPU_OK &&
         wtfgpu_read_dirty_counts(ctx_, 0, n, dc.data()) == WTFGPU_OK)
-      for (uint32_t l = 0; l < n; l++) stats_.alg_bytes += nb[l] + 2ull * 4096 * dc[l] + Testcases[l].second;
+      for (uint32_t l = 0; l < n; l++) stats_.alg_bytes += b_exec(nb[l], dc[l], Testcases[l].second);
   }
   const auto tc = Clock::now();
   std::vector<uint32_t> timedout;
@@ -1711,7 +1736,7 @@ void GpuBackend_t::collect_coverage(const std::vector<uint32_t> &lanes, std::vec
 }
 
 uint32_t GpuBackend_t::FreeLanes() const {
-  if (busy_.empty()) return parts_n() > 1 ? nlanes_ / 2 : nlanes_;
+  if (parts_.empty()) return parts_n() > 1 ? nlanes_ / 2 : nlanes_;  // streaming not set up yet
   const Part &P = parts_[next_part_];
   if (P.launched) return P.hi - P.lo;  // its running lanes may all finish: an upper bound
   return (uint32_t)P.free.size();
@@ -1735,28 +1760,7 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
                               std::vector<StreamResult_t> &Out, ModuleSlots *Slots, size_t *Taken) {
   const auto t0 = Clock::now();
   if (Taken) *Taken = 0;
-  if (busy_.empty()) {
-    busy_.assign(nlanes_, 0);
-    tag_.assign(nlanes_, 0);
-    tc_bytes_.assign(nlanes_, 0);
-    ordered_.assign(nlanes_, 0);
-    lres_.assign(nlanes_, LaneResult{});
-    plain_.assign(nlanes_, 0);
-    const uint32_t n = parts_n();
-    done_.assign((nlanes_ + n - 1) / n + 1, 0);
-    parts_.assign(n, Part{});
-    for (uint32_t p = 0; p < n; p++) {
-      Part &Q = parts_[p];
-      Q.lo = (uint32_t)((uint64_t)nlanes_ * p / n);
-      Q.hi = (uint32_t)((uint64_t)nlanes_ * (p + 1) / n);
-      Q.free.resize(Q.hi - Q.lo);
-      for (uint32_t l = Q.lo; l < Q.hi; l++) Q.free[l - Q.lo] = l;
-    }
-    // every lane idle until it gets a testcase
-    std::vector<uint32_t> all(nlanes_);
-    for (uint32_t l = 0; l < nlanes_; l++) all[l] = l;
-    if (wtfgpu_stop(ctx_, all.data(), nlanes_, WTFGPU_EXIT_IDLE)) return false;
-  }
+  if (parts_.empty() && !setup_parts()) return false;
   const bool pipelined = parts_.size() > 1;
   const uint32_t pi = next_part_;
   next_part_ = (next_part_ + 1) % (uint32_t)parts_.size();
@@ -1766,230 +1770,34 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
   const auto ti = Clock::now();
   stats_.harvest_ms += std::chrono::duration<double, std::milli>(ti - t0).count();
   // ---- refill: the lowest free lanes, in order
-  std::vector<uint32_t> &fresh = fresh_;
-  {
-    const size_t take = std::min(In.size(), P.free.size());
-    fresh.assign(P.free.begin(), P.free.begin() + (std::ptrdiff_t)take);
-    P.free.erase(P.free.begin(), P.free.begin() + (std::ptrdiff_t)take);
-  }
-  if (Taken) *Taken = fresh.size();
+  const size_t n = std::min(In.size(), P.free.size());
+  fresh_.assign(P.free.begin(), P.free.begin() + (std::ptrdiff_t)n);
+  P.free.erase(P.free.begin(), P.free.begin() + (std::ptrdiff_t)n);
+  if (Taken) *Taken = n;
   stats_.fresh_ms += ms_since(ti);
-  if (!fresh.empty()) {
-    if (wtfgpu_restore_lanes(ctx_, fresh.data(), (uint32_t)fresh.size())) return false;
+  if (n) {
+    if (wtfgpu_restore_lanes(ctx_, fresh_.data(), (uint32_t)n)) return false;
     stats_.restore_dev_ms += ms_since(ti);
-    // One pass over the fresh lanes, a chunk of them per loop index: the
-    // lane's view and streaming state are reset; a prepared insert
-    // (Target_t::PrepareInsert) the backend takes is applied, with the lane's
-    // module state reset as before an InsertTestcase, and its feed's size
-    // noted (the chunk's sum with it); the other lanes are listed for the
-    // InsertTestcase calls below, the lanes that hold a result already for
-    // the device stop.
-    const size_t n = fresh.size();
-    const bool feeds = feed_action_ || insert_action_;
-    constexpr size_t kChunk = 1024;
-    const size_t chunks = (n + kChunk - 1) / kChunk;
-    if (rchunks_.size() < chunks) rchunks_.resize(chunks);
-    if (flen_.size() < n) {
-      flen_.resize(n);
-      fhas_.resize(n);
-      foff_.resize(n + 1);
-    }
-    HostPool::Get().For(chunks, 1, [&](size_t c) {
-      RefillChunk &C = rchunks_[c];
-      C.call.clear();
-      C.pre.clear();
-      C.bytes = 0;
-      const size_t hi = std::min(n, (c + 1) * kChunk);
-      for (size_t i = c * kChunk; i < hi; i++) {
-        const uint32_t l = fresh[i];
-        // a view the host touched goes back to the initial state; an untouched
-        // one still is in it (the common case: no host handler ran on the lane)
-        if (touched_[l]) reset_view(l);
-        PrepFeed f{};
-        busy_[l] = 1;
-        tag_[l] = In[i].tag;
-        tc_bytes_[l] = In[i].size;
-        const StreamTestcase_t &T = In[i];
-        ordered_[l] = T.ordered;
-        if (T.ordered) {  // made on the device below: no bytes, no InsertTestcase
-          pf_[l] = f;
-          flen_[i] = 0;
-          fhas_[i] = 0;
-          if (Slots) Slots->ResetLane(l);
-          continue;
-        }
-        bool prepared = true;
-        switch (T.prep) {
-          case PreparedInsert_t::Call: prepared = false; break;
-          case PreparedInsert_t::Failed:
-            view(l).result = Crash_t("insert-testcase-failed");
-            C.pre.push_back(l);
-            break;
-          case PreparedInsert_t::Nothing: break;
-          case PreparedInsert_t::Feed:  // SetFeed would refuse it: InsertTestcase keeps its host path
-            if (!feed_action_ || T.prep_size > kFeedRegion)
-              prepared = false;
-            else
-              f = PrepFeed{T.prep_data, (uint32_t)T.prep_size, 1, 0};
-            break;
-          case PreparedInsert_t::Insert:  // as SetInsert
-            if (!insert_action_ || T.size + 4 > kFeedRegion)
-              prepared = false;
-            else
-              f = PrepFeed{T.data, (uint32_t)T.size, 1, 1};
-            break;
-        }
-        pf_[l] = f;
-        flen_[i] = f.has ? f.len + (f.ins ? 4 : 0) : 0;
-        fhas_[i] = f.has;
-        C.bytes += flen_[i];
-        if (!prepared) {
-          C.call.push_back((uint32_t)i);
-          continue;
-        }
-        if (Slots) Slots->ResetLane(l);
-      }
-    }, n >= 512);
-    recycle_arenas();  // reset_view's drop_staged ran inside the loop
-    const auto tm = Clock::now();
-    stats_.restore_ms += std::chrono::duration<double, std::milli>(tm - ti).count();
-    call_.clear();
-    pre_.clear();
-    for (size_t c = 0; c < chunks; c++) {
-      call_.insert(call_.end(), rchunks_[c].call.begin(), rchunks_[c].call.end());
-      pre_.insert(pre_.end(), rchunks_[c].pre.begin(), rchunks_[c].pre.end());
-    }
-    stats_.prepared += n - call_.size();
-    std::vector<uint32_t> call(call_.size());
-    if (!call_.empty()) {  // InsertTestcase on the host for the lanes no prepared insert covers
-      std::vector<std::pair<const uint8_t *, size_t>> call_tcs(call_.size());
-      for (size_t k = 0; k < call_.size(); k++) {
-        call[k] = fresh[call_[k]];
-        call_tcs[k] = {In[call_[k]].data, In[call_[k]].size};
-      }
-      std::vector<uint8_t> ok;
-      insert_lanes(Target, call, call_tcs, Slots, ok);
-      for (size_t k = 0; k < call.size(); k++)
-        if (!ok[k]) view(call[k]).result = Crash_t("insert-testcase-failed");
-    }
+    refill_pass(In, Slots);
+    stats_.restore_ms += ms_since(ti);
+    if (!insert_unprepared(Target, In, Slots)) return false;  // module_ms, and upload_ms over its flush
     const auto tu = Clock::now();
-    stats_.module_ms += std::chrono::duration<double, std::milli>(tu - tm).count();
-    if (flush_lanes(call)) return false;
-    if (!call_.empty()) {
-      // their feeds (a view's SetFeed / SetInsert bytes) and results, now known
-      std::vector<uint32_t> pre_call;
-      for (size_t k = 0; k < call_.size(); k++) {
-        const uint32_t i = call_[k], l = call[k];
-        if (!touched_[l]) continue;
-        const LaneView &v = views_[l];
-        flen_[i] = (uint32_t)v.feed.size();
-        fhas_[i] = v.has_feed;
-        rchunks_[i / kChunk].bytes += flen_[i];
-        if (v.result.has_value()) pre_call.push_back(l);
-      }
-      if (!pre_call.empty()) {  // both ascending
-        tmp_lanes_.resize(pre_.size() + pre_call.size());
-        std::merge(pre_.begin(), pre_.end(), pre_call.begin(), pre_call.end(), tmp_lanes_.begin());
-        pre_.swap(tmp_lanes_);
-      }
-    }
-    // --device-mutate: the ordered lanes, ascending as the fresh lanes are
-    mut_lanes_.clear();
-    mut_idx_.clear();
-    mut_nc_.clear();
-    uint32_t min_entry = 0, min_op = 0;  // `minimize`: one entry and op a step
-    if (mut_on_ || pkt_on_ || min_on_)
-      for (size_t i = 0; i < n; i++)
-        if (In[i].ordered) {
-          if (In[i].minimize != min_on_) return false;
-          if (min_on_ && !mut_lanes_.empty() && (In[i].min_entry != min_entry || In[i].min_op != min_op)) return false;
-          min_entry = In[i].min_entry;
-          min_op = In[i].min_op;
-          mut_lanes_.push_back(fresh[i]);
-          mut_idx_.push_back(In[i].index);
-          mut_nc_.push_back(In[i].ncorpus);
-        }
+    if (!list_ordered(In)) return false;
     // (lanes refilled with bytes in the same step keep the upload path; an
     // ordered lane has no feed there, and gets its own right after)
-    if (feeds && mut_lanes_.size() < n) {
-      const auto tf = Clock::now();
-      // the chunks' first offsets, then each chunk's lanes packed into the
-      // part's pinned buffer on all host threads: one DMA
-      uint64_t total = 0;
-      for (size_t c = 0; c < chunks; c++) {
-        const uint64_t b = rchunks_[c].bytes;
-        rchunks_[c].bytes = total;
-        total += b;
-      }
-      foff_[n] = total;
-      if (total > P.pin_cap) {
-        if (P.pin) wtfgpu_host_free(ctx_, P.pin);
-        P.pin = nullptr;
-        P.pin_cap = std::max<uint64_t>(total * 2, 1 << 20);
-        void *p = nullptr;
-        if (wtfgpu_host_alloc(ctx_, P.pin_cap, &p)) return false;
-        P.pin = (uint8_t *)p;
-      }
-      HostPool::Get().For(chunks, 1, [&](size_t c) {
-        uint64_t at = rchunks_[c].bytes;
-        const size_t hi = std::min(n, (c + 1) * kChunk);
-        for (size_t i = c * kChunk; i < hi; i++) {
-          foff_[i] = at;
-          if (!flen_[i]) continue;
-          const uint32_t l = fresh[i];
-          const PrepFeed &f = pf_[l];
-          uint8_t *o = P.pin + at;
-          if (f.has) {
-            if (f.ins) {
-              memcpy(o, &f.len, 4);
-              o += 4;
-            }
-            if (f.len) memcpy(o, f.p, f.len);
-          } else {
-            memcpy(o, views_[l].feed.data(), flen_[i]);
-          }
-          at += flen_[i];
-        }
-      }, n >= 512);
-      if (wtfgpu_set_feed_lanes(ctx_, fresh.data(), (uint32_t)n, foff_.data(), fhas_.data(), P.pin, total))
-        return false;
-      stats_.up_feed_ms += ms_since(tf);
-    }
-    if (!mut_lanes_.empty()) {
-      const auto tmu = Clock::now();
-      if (min_on_) {
-        if (wtfgpu_minimize_feed_lanes(ctx_, mut_lanes_.data(), (uint32_t)mut_lanes_.size(), min_entry, min_op,
-                                       mut_idx_.data()) != WTFGPU_OK)
-          return false;
-      } else if (pkt_on_) {
-        const wtfgpu_packet_params_t pp{pkt_.GenMaxPackets, pkt_.GenCommands, pkt_.GenMaxBody, pkt_.FlipOneIn,
-                                        pkt_.InsertMaxPackets};
-        if (wtfgpu_mutate_packets_lanes(ctx_, mut_lanes_.data(), (uint32_t)mut_lanes_.size(), mut_seed_,
-                                        mut_idx_.data(), mut_nc_.data(), &pp) != WTFGPU_OK)
-          return false;
-      } else if (wtfgpu_mutate_feed_lanes(ctx_, mut_lanes_.data(), (uint32_t)mut_lanes_.size(), mut_seed_,
-                                          mut_idx_.data(), mut_nc_.data(), mut_max_len_) != WTFGPU_OK) {
-        return false;
-      }
-      stats_.mutate_dev_ms += ms_since(tmu);
-    }
+    if ((feed_action_ || insert_action_) && mut_lanes_.size() < n && !upload_feeds(P)) return false;
+    if (!mut_lanes_.empty() && !make_ordered()) return false;
     // lanes InsertTestcase stopped never run: marked STOPPED on the device, so
     // the next classification gives them their result
     if (!pre_.empty() && wtfgpu_stop(ctx_, pre_.data(), (uint32_t)pre_.size(), WTFGPU_EXIT_STOPPED) != WTFGPU_OK)
       return false;
     stats_.upload_ms += ms_since(tu);
-    stats_.testcases += fresh.size();
+    stats_.testcases += n;
   }
   stats_.insert_ms += ms_since(ti);
-  // ---- one slice over the part's occupied lanes
+  // ---- one slice over the part's occupied lanes: those still running plus the refilled ones
   const auto to = Clock::now();
-  if (P.occ.empty()) {  // occupied: the lanes still running plus the refilled ones (both ascending)
-    P.occ.swap(fresh);
-  } else if (!fresh.empty()) {
-    tmp_lanes_.resize(P.occ.size() + fresh.size());
-    std::merge(P.occ.begin(), P.occ.end(), fresh.begin(), fresh.end(), tmp_lanes_.begin());
-    P.occ.swap(tmp_lanes_);
-  }
+  merge_lanes(P.occ, fresh_);
   stats_.occ_ms += ms_since(to);
   if (!P.occ.empty()) {
     const auto tk = Clock::now();
@@ -2003,28 +1811,242 @@ bool GpuBackend_t::StreamStep(const Target_t &Target, const std::vector<StreamTe
   return true;
 }
 
+// First call: the parts' ranges and free lists, the per-lane state, every lane idle until it gets a testcase.
+bool GpuBackend_t::setup_parts() {
+  tag_.assign(nlanes_, 0);
+  tc_bytes_.assign(nlanes_, 0);
+  ordered_.assign(nlanes_, 0);
+  lres_.assign(nlanes_, LaneResult{});
+  plain_.assign(nlanes_, 0);
+  const uint32_t n = parts_n();
+  done_.assign((nlanes_ + n - 1) / n + 1, 0);
+  parts_.assign(n, Part{});
+  for (uint32_t p = 0; p < n; p++) {
+    Part &Q = parts_[p];
+    Q.lo = (uint32_t)((uint64_t)nlanes_ * p / n);
+    Q.hi = (uint32_t)((uint64_t)nlanes_ * (p + 1) / n);
+    Q.free.resize(Q.hi - Q.lo);
+    for (uint32_t l = Q.lo; l < Q.hi; l++) Q.free[l - Q.lo] = l;
+  }
+  std::vector<uint32_t> all(nlanes_);
+  for (uint32_t l = 0; l < nlanes_; l++) all[l] = l;
+  return wtfgpu_stop(ctx_, all.data(), nlanes_, WTFGPU_EXIT_IDLE) == WTFGPU_OK;
+}
+
+// `into` becomes its merge with `add` (both ascending)
+void GpuBackend_t::merge_lanes(std::vector<uint32_t> &into, const std::vector<uint32_t> &add) {
+  if (add.empty()) return;
+  tmp_lanes_.resize(into.size() + add.size());
+  std::merge(into.begin(), into.end(), add.begin(), add.end(), tmp_lanes_.begin());
+  into.swap(tmp_lanes_);
+}
+
+// The refill's one pass over the fresh lanes, a chunk of them per loop index:
+// the lane's view and streaming state are reset; a prepared insert
+// (Target_t::PrepareInsert) the backend takes is applied, with the lane's
+// module state reset as before an InsertTestcase, and its feed's size noted
+// (the chunk's sum with it); the other lanes are listed for the
+// InsertTestcase calls (insert_unprepared), the lanes that hold a result
+// already for the device stop.
+void GpuBackend_t::refill_pass(const std::vector<StreamTestcase_t> &In, ModuleSlots *Slots) {
+  const size_t n = fresh_.size(), chunks = (n + kRefillChunk - 1) / kRefillChunk;
+  if (rchunks_.size() < chunks) rchunks_.resize(chunks);
+  if (flen_.size() < n) {
+    flen_.resize(n);
+    fhas_.resize(n);
+    foff_.resize(n + 1);
+  }
+  HostPool::Get().For(chunks, 1, [&](size_t c) {
+    RefillChunk &C = rchunks_[c];
+    C.call.clear();
+    C.pre.clear();
+    C.bytes = 0;
+    const size_t hi = std::min(n, (c + 1) * kRefillChunk);
+    for (size_t i = c * kRefillChunk; i < hi; i++) {
+      const uint32_t l = fresh_[i];
+      // a view the host touched goes back to the initial state; an untouched
+      // one still is in it (the common case: no host handler ran on the lane)
+      if (touched_[l]) reset_view(l);
+      PrepFeed f{};
+      tag_[l] = In[i].tag;
+      tc_bytes_[l] = In[i].size;
+      const StreamTestcase_t &T = In[i];
+      ordered_[l] = T.ordered;
+      bool prepared = true;
+      // (an ordered testcase is made on the device, make_ordered: no bytes, no InsertTestcase)
+      switch (T.ordered ? PreparedInsert_t::Nothing : T.prep) {
+        case PreparedInsert_t::Call: prepared = false; break;
+        case PreparedInsert_t::Failed:
+          view(l).result = Crash_t("insert-testcase-failed");
+          C.pre.push_back(l);
+          break;
+        case PreparedInsert_t::Nothing: break;
+        case PreparedInsert_t::Feed:  // SetFeed would refuse it: InsertTestcase keeps its host path
+          if (!feed_action_ || T.prep_size > kFeedRegion)
+            prepared = false;
+          else
+            f = PrepFeed{T.prep_data, (uint32_t)T.prep_size, 1, 0};
+          break;
+        case PreparedInsert_t::Insert:  // as SetInsert
+          if (!insert_action_ || T.size + 4 > kFeedRegion)
+            prepared = false;
+          else
+            f = PrepFeed{T.data, (uint32_t)T.size, 1, 1};
+          break;
+      }
+      pf_[l] = f;
+      flen_[i] = f.has ? f.len + (f.ins ? 4 : 0) : 0;
+      fhas_[i] = f.has;
+      C.bytes += flen_[i];
+      if (!prepared)
+        C.call.push_back((uint32_t)i);
+      else if (Slots)
+        Slots->ResetLane(l);
+    }
+  }, n >= 512);
+  recycle_arenas();  // reset_view's drop_staged ran inside the loop
+}
+
+// InsertTestcase on the host for the fresh lanes no prepared insert covers, its writes flushed;
+// their feeds (a view's SetFeed / SetInsert bytes) and results, now known, join the pass's.
+bool GpuBackend_t::insert_unprepared(const Target_t &Target, const std::vector<StreamTestcase_t> &In,
+                                     ModuleSlots *Slots) {
+  const auto tm = Clock::now();
+  const size_t n = fresh_.size(), chunks = (n + kRefillChunk - 1) / kRefillChunk;
+  call_.clear();
+  pre_.clear();
+  for (size_t c = 0; c < chunks; c++) {
+    call_.insert(call_.end(), rchunks_[c].call.begin(), rchunks_[c].call.end());
+    pre_.insert(pre_.end(), rchunks_[c].pre.begin(), rchunks_[c].pre.end());
+  }
+  stats_.prepared += n - call_.size();
+  std::vector<uint32_t> call(call_.size());
+  if (!call_.empty()) {
+    std::vector<std::pair<const uint8_t *, size_t>> call_tcs(call_.size());
+    for (size_t k = 0; k < call_.size(); k++) {
+      call[k] = fresh_[call_[k]];
+      call_tcs[k] = {In[call_[k]].data, In[call_[k]].size};
+    }
+    std::vector<uint8_t> ok;
+    insert_lanes(Target, call, call_tcs, Slots, ok);
+    for (size_t k = 0; k < call.size(); k++)
+      if (!ok[k]) view(call[k]).result = Crash_t("insert-testcase-failed");
+  }
+  const auto tu = Clock::now();
+  stats_.module_ms += std::chrono::duration<double, std::milli>(tu - tm).count();
+  if (flush_lanes(call)) return false;
+  std::vector<uint32_t> pre_call;
+  for (size_t k = 0; k < call_.size(); k++) {
+    const uint32_t i = call_[k], l = call[k];
+    if (!touched_[l]) continue;
+    const LaneView &v = views_[l];
+    flen_[i] = (uint32_t)v.feed.size();
+    fhas_[i] = v.has_feed;
+    rchunks_[i / kRefillChunk].bytes += flen_[i];
+    if (v.result.has_value()) pre_call.push_back(l);
+  }
+  merge_lanes(pre_, pre_call);
+  stats_.upload_ms += ms_since(tu);
+  return true;
+}
+
+// --device-mutate, --device-packets, `minimize`: the ordered lanes, ascending
+// as the fresh lanes are; `minimize` orders one entry and op a step.
+bool GpuBackend_t::list_ordered(const std::vector<StreamTestcase_t> &In) {
+  mut_lanes_.clear();
+  mut_idx_.clear();
+  mut_nc_.clear();
+  if (mut_on_ || pkt_on_ || min_on_)
+    for (size_t i = 0; i < fresh_.size(); i++)
+      if (In[i].ordered) {
+        if (In[i].minimize != min_on_) return false;
+        if (min_on_ && !mut_lanes_.empty() && (In[i].min_entry != min_entry_ || In[i].min_op != min_op_)) return false;
+        min_entry_ = In[i].min_entry;
+        min_op_ = In[i].min_op;
+        mut_lanes_.push_back(fresh_[i]);
+        mut_idx_.push_back(In[i].index);
+        mut_nc_.push_back(In[i].ncorpus);
+      }
+  return true;
+}
+
+// The fresh lanes' feeds: the chunks' first offsets, then each chunk's lanes
+// packed into the part's pinned buffer on all host threads: one DMA.
+bool GpuBackend_t::upload_feeds(Part &P) {
+  const auto tf = Clock::now();
+  const size_t n = fresh_.size(), chunks = (n + kRefillChunk - 1) / kRefillChunk;
+  uint64_t total = 0;
+  for (size_t c = 0; c < chunks; c++) {
+    const uint64_t b = rchunks_[c].bytes;
+    rchunks_[c].bytes = total;
+    total += b;
+  }
+  foff_[n] = total;
+  if (!fit_pinned(P.pin, P.pin_cap, total, std::max<uint64_t>(total * 2, 1 << 20))) return false;
+  HostPool::Get().For(chunks, 1, [&](size_t c) {
+    uint64_t at = rchunks_[c].bytes;
+    const size_t hi = std::min(n, (c + 1) * kRefillChunk);
+    for (size_t i = c * kRefillChunk; i < hi; i++) {
+      foff_[i] = at;
+      if (!flen_[i]) continue;
+      const uint32_t l = fresh_[i];
+      const PrepFeed &f = pf_[l];
+      uint8_t *o = P.pin + at;
+      if (f.has) {
+        if (f.ins) {
+          memcpy(o, &f.len, 4);
+          o += 4;
+        }
+        if (f.len) memcpy(o, f.p, f.len);
+      } else {
+        memcpy(o, views_[l].feed.data(), flen_[i]);
+      }
+      at += flen_[i];
+    }
+  }, n >= 512);
+  if (wtfgpu_set_feed_lanes(ctx_, fresh_.data(), (uint32_t)n, foff_.data(), fhas_.data(), P.pin, total)) return false;
+  stats_.up_feed_ms += ms_since(tf);
+  return true;
+}
+
+// The one device call that makes the ordered lanes' testcases.
+bool GpuBackend_t::make_ordered() {
+  const auto tmu = Clock::now();
+  const uint32_t m = (uint32_t)mut_lanes_.size();
+  int rc;
+  if (min_on_) {
+    rc = wtfgpu_minimize_feed_lanes(ctx_, mut_lanes_.data(), m, min_entry_, min_op_, mut_idx_.data());
+  } else if (pkt_on_) {
+    const wtfgpu_packet_params_t pp{pkt_.GenMaxPackets, pkt_.GenCommands, pkt_.GenMaxBody, pkt_.FlipOneIn,
+                                    pkt_.InsertMaxPackets};
+    rc = wtfgpu_mutate_packets_lanes(ctx_, mut_lanes_.data(), m, mut_seed_, mut_idx_.data(), mut_nc_.data(), &pp);
+  } else {
+    rc = wtfgpu_mutate_feed_lanes(ctx_, mut_lanes_.data(), m, mut_seed_, mut_idx_.data(), mut_nc_.data(),
+                                  mut_max_len_);
+  }
+  if (rc != WTFGPU_OK) return false;
+  stats_.mutate_dev_ms += ms_since(tmu);
+  return true;
+}
+
+// the part's pinned exit records, one per lane (grown to the exact size)
+bool GpuBackend_t::fit_exits(Part &P) {
+  const uint64_t bytes = (uint64_t)(P.hi - P.lo) * sizeof(wtfgpu_exit_t);
+  return fit_pinned(P.ex, P.ex_cap, bytes, bytes);
+}
+
 // The slice's read-back queued behind it on the part's queue (exits, byte and
 // dirty counts, StopWithArgs arguments, the stopped lanes' coverage), into
 // pinned buffers the harvest reads after wtfgpu_run_wait without a device
 // call of its own. false: nothing queued (the harvest reads them itself).
 bool GpuBackend_t::prefetch_part(Part &P) {
   const uint32_t count = P.hi - P.lo;
-  auto grow = [&](auto *&p, uint64_t bytes) {
-    if (p) return true;
-    void *q = nullptr;
-    if (wtfgpu_host_alloc(ctx_, bytes, &q)) return false;
-    p = (std::remove_reference_t<decltype(p)>)q;
-    return true;
+  auto grow = [&](auto *&p, uint64_t bytes) {  // allocated once
+    uint64_t cap = p ? bytes : 0;
+    return fit_pinned(p, cap, bytes, bytes);
   };
-  if (P.ex_cap < count) {
-    if (P.ex) wtfgpu_host_free(ctx_, P.ex);
-    P.ex = nullptr;
-    P.ex_cap = 0;
-    if (!grow(P.ex, (uint64_t)count * sizeof(wtfgpu_exit_t))) return false;
-    P.ex_cap = count;
-  }
   const bool args = !args_results_.empty();
-  if (!grow(P.nb, (uint64_t)count * 8) || !grow(P.dc, (uint64_t)count * 4) || !grow(P.cov_hdr, 16) ||
+  if (!fit_exits(P) || !grow(P.nb, (uint64_t)count * 8) || !grow(P.dc, (uint64_t)count * 4) || !grow(P.cov_hdr, 16) ||
       (args && !grow(P.sargs, (uint64_t)count * 48)))
     return false;
   if (wtfgpu_prefetch_results(ctx_, P.lo, count, P.ex, P.nb, P.dc, args ? P.sargs : nullptr) != WTFGPU_OK)
@@ -2046,9 +2068,39 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
   stats_.run_ms += std::chrono::duration<double, std::milli>(te - tw).count();
   account_run(rs);
   P.launched = false;
-  const uint32_t first = P.lo, count = P.hi - P.lo;
-  // the results handed out at this part's last harvest were consumed before
-  // this call: cleared (capacity kept) before this slice's go in
+  clear_results(P);
+  // prefetched (P.pf), the exits (and counts, arguments, coverage count) are in P's pinned buffers
+  if (!P.pf && (!fit_exits(P) || wtfgpu_read_exits(ctx_, P.lo, P.hi - P.lo, P.ex))) return false;
+  uint64_t bytes = classify_part(P);  // B_exec of the finished lanes, from the prefetched counts
+  name_stop_args(named_, P.lo, P.ex, done_, &lres_, P.pf ? P.sargs : nullptr);
+  stats_.exits_ms += ms_since(te);
+  if (!hits_.empty() && !service_hits(hits_, P.lo, done_, Slots, Slots != nullptr)) return false;
+  bytes += settle_late(P);
+  P.occ.swap(run_);  // the lanes still occupied
+  if (fin_.empty()) return true;
+  if (want_gprs_ && !fill_lanes(fin_, P.lo, P.ex, lres_)) return false;
+  const auto tc = Clock::now();
+  account_bytes(P, bytes);
+  stats_.bytes_ms += ms_since(tc);
+  collect_coverage(fin_, lres_, P.pf && P.pf_cov ? P.cov_hdr : nullptr);
+  if (cov_check_failed_) return false;
+  unplain_covered(P);
+  const auto tr = Clock::now();
+  stats_.coverage_ms += std::chrono::duration<double, std::milli>(tr - tc).count();
+  target_restore(Target, fin_, Slots);
+  stats_.target_restore_ms += ms_since(tr);
+  const auto tout = Clock::now();
+  if (!read_back_kept(P)) return false;
+  write_out(P, Out);
+  merge_lanes(P.free, fin_);  // the finished lanes join the free ones
+  stats_.out_ms += ms_since(tout);
+  stats_.batches++;
+  return true;
+}
+
+// The results handed out at this part's last harvest were consumed before
+// this call: cleared (capacity kept) before this slice's go in.
+void GpuBackend_t::clear_results(Part &P) {
   HostPool::Get().For(P.res_used.size(), 1024, [&](size_t i) {
     LaneResult &r = lres_[P.res_used[i]];
     r.result = Ok_t();
@@ -2063,32 +2115,21 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
     r.cov_overflow = false;
   }, P.res_used.size() >= 8192);
   P.res_used.clear();
-  const bool pf = P.pf;  // the exits (and counts, arguments, coverage count) are in P's pinned buffers
-  P.pf = false;
-  if (!pf) {
-    if (P.ex_cap < count) {
-      if (P.ex) wtfgpu_host_free(ctx_, P.ex);
-      P.ex = nullptr;
-      P.ex_cap = 0;
-      void *p = nullptr;
-      if (wtfgpu_host_alloc(ctx_, (uint64_t)count * sizeof(wtfgpu_exit_t), &p)) return false;
-      P.ex = (wtfgpu_exit_t *)p;
-      P.ex_cap = count;
-    }
-    if (wtfgpu_read_exits(ctx_, first, count, P.ex)) return false;
-  }
-  // One pass over the part's occupied lanes, a chunk of them per loop index.
-  // Each lane's exit record is read once: the exit is classified (as
-  // classify does), a finished lane's result written (fill_lane) and its
-  // B_exec bytes added to the chunk's sum. The common exit, Stop(Ok) on a view
-  // the host never touched, gets no LaneResult: the lane is only marked plain
-  // (not when registers are wanted: those results are filled after the pass).
-  // The chunk lists the finished lanes, the ones still running, the
-  // breakpoint hits for the host and the StopWithArgs exits to be named.
+}
+
+// The harvest's one pass over the part's occupied lanes, a chunk of them per
+// loop index. Each lane's exit record is read once: the exit is classified
+// (classify_exit), a finished lane's result written (fill_lane) and its
+// B_exec bytes added to the chunk's sum. The common exit, Stop(Ok) on a view
+// the host never touched, gets no LaneResult: the lane is only marked plain
+// (not when registers are wanted: those results are filled after the pass).
+// The chunk lists the finished lanes, the ones still running, the breakpoint
+// hits for the host and the StopWithArgs exits to be named; the chunks' lists in chunk order, ascending,
+// make fin_, P.res_used, run_, hits_ and named_. Returns fin_'s B_exec (when the counts were prefetched).
+uint64_t GpuBackend_t::classify_part(Part &P) {
   const wtfgpu_exit_t *ex = P.ex;
-  const size_t n = P.occ.size();
-  constexpr size_t kChunk = 2048;
-  const size_t chunks = (n + kChunk - 1) / kChunk;
+  const uint32_t first = P.lo;
+  const size_t n = P.occ.size(), chunks = (n + kHarvestChunk - 1) / kHarvestChunk;
   if (hchunks_.size() < chunks) hchunks_.resize(chunks);
   const bool fill = !want_gprs_;
   // with a coverage target every finished lane gets a LaneResult: the verdict
@@ -2102,237 +2143,168 @@ bool GpuBackend_t::harvest_part(Part &P, const Target_t &Target, std::vector<Str
     C.hits.clear();
     C.named.clear();
     uint64_t bytes = 0;
-    const size_t hi = std::min(n, (c + 1) * kChunk);
-    for (size_t i = c * kChunk; i < hi; i++) {
+    const size_t hi = std::min(n, (c + 1) * kHarvestChunk);
+    for (size_t i = c * kHarvestChunk; i < hi; i++) {
       const uint32_t l = P.occ[i];
       const wtfgpu_exit_t &e = ex[l - first];
-      // a view the host has not touched since its reset holds no result: the
-      // common exits (Stop(Ok), still running, a breakpoint) leave it so
-      LaneView &v = views_[l];
-      const auto mark = [&]() -> LaneView & {
-        touched_[l] = 1;
-        return v;
-      };
-      bool plain = false, direct = false;
-      // a result the exit alone decides: on a view the host never touched it
-      // goes straight into the lane's LaneResult (the view stays untouched, so
-      // the refill has nothing to reset); else through the view, as classify's
-      const auto ends = [&](TestcaseResult_t &&R) {
-        if (fill && !touched_[l]) {
-          lres_[l].result = std::move(R);
-          direct = true;
-        } else {
-          mark().result = std::move(R);
-        }
-      };
-      switch (e.status) {
-        case WTFGPU_EXIT_BREAKPOINT: C.hits.push_back(l); continue;
-        case WTFGPU_RUNNING: C.run.push_back(l); continue;  // sliced: still running when the slice ended
-        case WTFGPU_EXIT_STOP_ARGS: C.named.push_back(l); continue;
-        case WTFGPU_EXIT_TIMEOUT: ends(Timedout_t()); break;
-        case WTFGPU_EXIT_INT3:
-        case WTFGPU_EXIT_HLT: ends(Crash_t()); break;
-        case WTFGPU_EXIT_CR3: ends(Cr3Change_t()); break;
-        case WTFGPU_EXIT_FAULT: ends(FaultToResult(e.vector, e.error, e.rip, e.addr, e.opcode)); break;
-        case WTFGPU_EXIT_STOPPED: break;
-        case WTFGPU_EXIT_STOP_OK:  // device Feed action: Stop(Ok_t()) (an untouched view reads as Ok already)
-          if (touched_[l])
-            v.result = Ok_t();
-          else
-            plain = counted;
-          break;
-        case WTFGPU_EXIT_FEED_FAULT: mark().handler_fault = true; break;  // U43: fill_lane makes it an engine error
-        default:  // the engine cannot finish the testcase (see classify)
-          lres_[l].error = true;
-          if (!v.result) mark().result = Crash_t();
-          if (e.status == WTFGPU_EXIT_UNIMPLEMENTED) {
-            stats_.err_unimpl++;
-            stats_.unimpl_ops.add(e.opcode);
-            stats_.last_unimpl_op = e.opcode;
-            stats_.last_unimpl_rip = e.rip;
-          } else if (e.status == WTFGPU_EXIT_OVERLAY_FULL) {
-            stats_.err_overlay++;
-          } else {
-            stats_.err_other++;
-          }
-          break;
+      const ExitClass x = classify_exit(l, e, &lres_[l], fill);
+      if (x.kind != ExitClass::Finished) {
+        (x.kind == ExitClass::Hit ? C.hits : x.kind == ExitClass::Running ? C.run : C.named).push_back(l);
+        continue;
       }
       C.fin.push_back(l);
-      if (plain) {
+      if (x.ok && counted) {
         plain_[l] = 1;
       } else {
         C.used.push_back(l);
-        if (direct) {  // as fill_lane on an untouched view, the result in place already
-          LaneResult &r = lres_[l];
-          r.rip = e.rip;
-          r.icount = e.icount;
-          r.exit_status = e.status;
-        } else if (fill) {
-          fill_lane(l, e, lres_[l]);
-        }
+        if (fill) fill_lane(l, e, lres_[l], x.direct);
       }
-      // B_exec = instruction + data bytes, testcase bytes, 2 x 4096 per dirty page
-      if (pf) bytes += P.nb[l - first] + 2ull * 4096 * P.dc[l - first] + tc_bytes_[l];
+      if (P.pf) bytes += b_exec(P.nb[l - first], P.dc[l - first], tc_bytes_[l]);
     }
     C.bytes = bytes;
   }, n >= 2048);
-  // the chunks' lists in chunk order: ascending
-  std::vector<uint32_t> &finished = fin_;
-  finished.clear();
+  fin_.clear();
   run_.clear();
   hits_.clear();
   named_.clear();
-  uint64_t b_exec = 0;
+  uint64_t bytes = 0;
   for (size_t c = 0; c < chunks; c++) {
     const HarvestChunk &C = hchunks_[c];
-    finished.insert(finished.end(), C.fin.begin(), C.fin.end());
+    fin_.insert(fin_.end(), C.fin.begin(), C.fin.end());
     P.res_used.insert(P.res_used.end(), C.used.begin(), C.used.end());
     run_.insert(run_.end(), C.run.begin(), C.run.end());
     hits_.insert(hits_.end(), C.hits.begin(), C.hits.end());
     named_.insert(named_.end(), C.named.begin(), C.named.end());
-    b_exec += C.bytes;
+    bytes += C.bytes;
   }
-  name_stop_args(named_, first, ex, done_, &lres_, pf ? P.sargs : nullptr);
-  stats_.exits_ms += ms_since(te);
-  if (!hits_.empty() && !service_hits(hits_, first, done_, Slots, Slots != nullptr)) return false;
-  if (!hits_.empty() || !named_.empty()) {
-    // the lanes the host named or serviced, in lane order: the finished ones
-    // join the finished list, the others stay occupied
-    late_.resize(hits_.size() + named_.size());
-    std::merge(hits_.begin(), hits_.end(), named_.begin(), named_.end(), late_.begin());
-    std::vector<uint32_t> late_fin, late_run;
-    for (uint32_t l : late_) {
-      (done_[l - first] ? late_fin : late_run).push_back(l);
-      done_[l - first] = 0;
-    }
-    if (fill) {
-      HostPool::Get().For(late_fin.size(), 1024, [&](size_t i) {
-        fill_lane(late_fin[i], ex[late_fin[i] - first], lres_[late_fin[i]]);
-      }, late_fin.size() >= 2048);
-    }
-    if (pf)
-      for (uint32_t l : late_fin) b_exec += P.nb[l - first] + 2ull * 4096 * P.dc[l - first] + tc_bytes_[l];
-    const auto join = [&](std::vector<uint32_t> &into, const std::vector<uint32_t> &add) {
-      if (add.empty()) return;
-      tmp_lanes_.resize(into.size() + add.size());
-      std::merge(into.begin(), into.end(), add.begin(), add.end(), tmp_lanes_.begin());
-      into.swap(tmp_lanes_);
-    };
-    join(finished, late_fin);
-    join(P.res_used, late_fin);
-    join(run_, late_run);
+  return bytes;
+}
+
+// The lanes the host named or serviced, in lane order: the finished ones join
+// the finished list (their results filled, their B_exec returned as
+// classify_part's), the others stay occupied.
+uint64_t GpuBackend_t::settle_late(Part &P) {
+  if (hits_.empty() && named_.empty()) return 0;
+  const uint32_t first = P.lo;
+  late_.resize(hits_.size() + named_.size());
+  std::merge(hits_.begin(), hits_.end(), named_.begin(), named_.end(), late_.begin());
+  std::vector<uint32_t> late_fin, late_run;
+  for (uint32_t l : late_) {
+    (done_[l - first] ? late_fin : late_run).push_back(l);
+    done_[l - first] = 0;
   }
-  P.occ.swap(run_);  // the lanes still occupied
-  if (finished.empty()) return true;
-  if (!fill && !fill_lanes(finished, first, ex, lres_)) return false;
-  const auto tc = Clock::now();
-  if (pf) {
-    stats_.alg_bytes += b_exec;
-  } else {
-    uint32_t lo = finished.front() & ~63u, hi = finished.back() + 1;
-    std::vector<uint64_t> nb(hi - lo);
-    std::vector<uint32_t> dc(hi - lo);
-    if (wtfgpu_read_bytes(ctx_, lo, hi - lo, nb.data()) == WTFGPU_OK &&
-        wtfgpu_read_dirty_counts(ctx_, lo, hi - lo, dc.data()) == WTFGPU_OK)
-      for (uint32_t l : finished) stats_.alg_bytes += nb[l - lo] + 2ull * 4096 * dc[l - lo] + tc_bytes_[l];
+  if (!want_gprs_)
+    HostPool::Get().For(late_fin.size(), 1024, [&](size_t i) {
+      fill_lane(late_fin[i], P.ex[late_fin[i] - first], lres_[late_fin[i]]);
+    }, late_fin.size() >= 2048);
+  uint64_t bytes = 0;
+  if (P.pf)
+    for (uint32_t l : late_fin) bytes += b_exec(P.nb[l - first], P.dc[l - first], tc_bytes_[l]);
+  merge_lanes(fin_, late_fin);
+  merge_lanes(P.res_used, late_fin);
+  merge_lanes(run_, late_run);
+  return bytes;
+}
+
+// B_exec of the finished lanes: the pass's sum when the counts were
+// prefetched, else the counts are read here.
+void GpuBackend_t::account_bytes(const Part &P, uint64_t prefetched) {
+  if (P.pf) {
+    stats_.alg_bytes += prefetched;
+    return;
   }
-  stats_.bytes_ms += ms_since(tc);
-  collect_coverage(finished, lres_, pf && P.pf_cov ? P.cov_hdr : nullptr);
-  if (cov_check_failed_) return false;
-  {  // a plain lane that reported new coverage gets its LaneResult after all (entries sorted by lane)
-    uint32_t last = ~0u;
-    size_t added = 0;
-    for (const std::pair<uint32_t, uint64_t> &E : cov_sorted_) {
-      const uint32_t l = E.first;
-      if (l == last) continue;
-      last = l;
-      if (!plain_[l] || lres_[l].new_coverage.empty()) continue;
-      plain_[l] = 0;
-      fill_lane(l, ex[l - first], lres_[l]);
-      P.res_used.push_back(l);
-      added++;
-    }
-    if (added) std::inplace_merge(P.res_used.begin(), P.res_used.end() - (std::ptrdiff_t)added, P.res_used.end());
+  const uint32_t lo = fin_.front() & ~63u, hi = fin_.back() + 1;
+  std::vector<uint64_t> nb(hi - lo);
+  std::vector<uint32_t> dc(hi - lo);
+  if (wtfgpu_read_bytes(ctx_, lo, hi - lo, nb.data()) == WTFGPU_OK &&
+      wtfgpu_read_dirty_counts(ctx_, lo, hi - lo, dc.data()) == WTFGPU_OK)
+    for (uint32_t l : fin_) stats_.alg_bytes += b_exec(nb[l - lo], dc[l - lo], tc_bytes_[l]);
+}
+
+// A plain lane that reported new coverage gets its LaneResult after all
+// (collect_coverage's entries, sorted by lane).
+void GpuBackend_t::unplain_covered(Part &P) {
+  uint32_t last = ~0u;
+  size_t added = 0;
+  for (const std::pair<uint32_t, uint64_t> &E : cov_sorted_) {
+    const uint32_t l = E.first;
+    if (l == last) continue;
+    last = l;
+    if (!plain_[l] || lres_[l].new_coverage.empty()) continue;
+    plain_[l] = 0;
+    fill_lane(l, P.ex[l - P.lo], lres_[l]);
+    P.res_used.push_back(l);
+    added++;
   }
-  const auto tr = Clock::now();
-  stats_.coverage_ms += std::chrono::duration<double, std::milli>(tr - tc).count();
-  target_restore(Target, finished, Slots);
-  stats_.target_restore_ms += ms_since(tr);
-  const auto tout = Clock::now();
-  // --device-mutate / --device-packets: the ordered testcases whose result is
-  // not the common counted one and whose bytes the session will look at (its
-  // filter; without one, all of them), read back packed in one call before
-  // their lanes are refilled: whole = 0 the mutator's chunk, whole = 1 the
-  // packet list's whole feed. The bytes stay in the engine's pinned buffer of
-  // this part's queue until the part's next harvest.
+  if (added) std::inplace_merge(P.res_used.begin(), P.res_used.end() - (std::ptrdiff_t)added, P.res_used.end());
+}
+
+// --device-mutate / --device-packets: the ordered testcases whose result is
+// not the common counted one and whose bytes the session will look at (its
+// filter; without one, all of them), read back packed in one call before
+// their lanes are refilled: whole = 0 the mutator's chunk, whole = 1 the
+// packet list's whole feed. The bytes stay in the engine's pinned buffer of
+// this part's queue until the part's next harvest.
+bool GpuBackend_t::read_back_kept(Part &P) {
   P.rb_lanes.clear();
   P.rb_bytes = nullptr;
-  if (mut_on_ || pkt_on_) {
-    P.rb_keepf.resize(finished.size());
-    HostPool::Get().For(finished.size(), 2048, [&](size_t i) {
-      const uint32_t l = finished[i];
-      P.rb_keepf[i] = !(ordered_[l] && !plain_[l]) ? 0 : (!rb_keep_ || rb_keep_(lres_[l])) ? 1 : 2;
-    }, finished.size() >= 8192);
-    for (size_t i = 0; i < finished.size(); i++) {
-      if (P.rb_keepf[i] == 1) P.rb_lanes.push_back(finished[i]);
-      stats_.readback_skipped += P.rb_keepf[i] == 2;
-    }
-    if (!P.rb_lanes.empty()) {
-      const auto trb = Clock::now();
-      const size_t m = P.rb_lanes.size();
-      P.rb_lens.resize(m);
-      P.rb_offs.resize(m);
-      uint64_t total = 0;
-      if (wtfgpu_read_feeds_packed(ctx_, P.rb_lanes.data(), (uint32_t)m, pkt_on_ ? 1 : 0, P.rb_lens.data(),
-                                   P.rb_offs.data(), &P.rb_bytes, &total) != WTFGPU_OK)
-        return false;
-      stats_.readback_ms += ms_since(trb);
-      const uint32_t longest = pkt_on_ ? (uint32_t)kFeedRegion : mut_max_len_;
-      for (size_t k = 0; k < m; k++)
-        if (P.rb_lens[k] > longest) return false;  // no feed (~0u), or not the mutator's chunk
-      if (pkt_on_) P.rb_tcs.resize(m);
-      stats_.readback_tcs += m;
-      stats_.readback_bytes += total;
-    }
+  if (!mut_on_ && !pkt_on_) return true;
+  P.rb_keepf.resize(fin_.size());
+  HostPool::Get().For(fin_.size(), 2048, [&](size_t i) {
+    const uint32_t l = fin_[i];
+    P.rb_keepf[i] = !(ordered_[l] && !plain_[l]) ? 0 : (!rb_keep_ || rb_keep_(lres_[l])) ? 1 : 2;
+  }, fin_.size() >= 8192);
+  for (size_t i = 0; i < fin_.size(); i++) {
+    if (P.rb_keepf[i] == 1) P.rb_lanes.push_back(fin_[i]);
+    stats_.readback_skipped += P.rb_keepf[i] == 2;
   }
+  if (P.rb_lanes.empty()) return true;
+  const auto trb = Clock::now();
+  const size_t m = P.rb_lanes.size();
+  P.rb_lens.resize(m);
+  P.rb_offs.resize(m);
+  uint64_t total = 0;
+  if (wtfgpu_read_feeds_packed(ctx_, P.rb_lanes.data(), (uint32_t)m, pkt_on_ ? 1 : 0, P.rb_lens.data(),
+                               P.rb_offs.data(), &P.rb_bytes, &total) != WTFGPU_OK)
+    return false;
+  stats_.readback_ms += ms_since(trb);
+  const uint32_t longest = pkt_on_ ? (uint32_t)kFeedRegion : mut_max_len_;
+  for (size_t k = 0; k < m; k++)
+    if (P.rb_lens[k] > longest) return false;  // no feed (~0u), or not the mutator's chunk
+  if (pkt_on_) P.rb_tcs.resize(m);
+  stats_.readback_tcs += m;
+  stats_.readback_bytes += total;
+  return true;
+}
+
+// The finished lanes' results, in lane order, appended to `Out`: a plain lane
+// as a count, the others with their LaneResult and, read back, their testcase.
+void GpuBackend_t::write_out(Part &P, std::vector<StreamResult_t> &Out) {
   const size_t base = Out.size();
-  Out.resize(base + finished.size());
-  HostPool::Get().For(finished.size(), 2048, [&](size_t i) {
-    const uint32_t l = finished[i];
+  Out.resize(base + fin_.size());
+  HostPool::Get().For(fin_.size(), 2048, [&](size_t i) {
+    const uint32_t l = fin_[i];
     if (plain_[l]) {
       plain_[l] = 0;
-      Out[base + i] = StreamResult_t{tag_[l], nullptr, ex[l - first].icount};
-    } else {
-      Out[base + i] = StreamResult_t{tag_[l], &lres_[l]};
-      if ((mut_on_ || pkt_on_) && P.rb_keepf[i] == 1) {
-        // its place in the read-back list (ascending, as finished is); a packet
-        // list becomes the testcase the target keeps here, on the pool
-        const size_t k = (size_t)(std::lower_bound(P.rb_lanes.begin(), P.rb_lanes.end(), l) - P.rb_lanes.begin());
-        const uint8_t *bytes = P.rb_bytes + P.rb_offs[k];
-        if (pkt_on_) {
-          P.rb_tcs[k] = pkt_.FeedToTestcase(bytes, P.rb_lens[k]);
-          Out[base + i].tc = (const uint8_t *)P.rb_tcs[k].data();
-          Out[base + i].tc_size = P.rb_tcs[k].size();
-        } else {
-          Out[base + i].tc = bytes;
-          Out[base + i].tc_size = P.rb_lens[k];
-        }
-        Out[base + i].has_tc = true;
-      }
+      Out[base + i] = StreamResult_t{tag_[l], nullptr, P.ex[l - P.lo].icount};
+      return;
     }
-    busy_[l] = 0;  // not runnable until refilled (a finished lane keeps its exit status)
-  }, finished.size() >= 8192);
-  // the finished lanes join the free ones (both ascending)
-  if (P.free.empty()) {
-    P.free.swap(finished);
-  } else {
-    tmp_lanes_.resize(P.free.size() + finished.size());
-    std::merge(P.free.begin(), P.free.end(), finished.begin(), finished.end(), tmp_lanes_.begin());
-    P.free.swap(tmp_lanes_);
-  }
-  stats_.out_ms += ms_since(tout);
-  stats_.batches++;
-  return true;
+    Out[base + i] = StreamResult_t{tag_[l], &lres_[l]};
+    if (!(mut_on_ || pkt_on_) || P.rb_keepf[i] != 1) return;
+    // its place in the read-back list (ascending, as fin_ is); a packet
+    // list becomes the testcase the target keeps here, on the pool
+    const size_t k = (size_t)(std::lower_bound(P.rb_lanes.begin(), P.rb_lanes.end(), l) - P.rb_lanes.begin());
+    const uint8_t *bytes = P.rb_bytes + P.rb_offs[k];
+    if (pkt_on_) {
+      P.rb_tcs[k] = pkt_.FeedToTestcase(bytes, P.rb_lens[k]);
+      Out[base + i].tc = (const uint8_t *)P.rb_tcs[k].data();
+      Out[base + i].tc_size = P.rb_tcs[k].size();
+    } else {
+      Out[base + i].tc = bytes;
+      Out[base + i].tc_size = P.rb_lens[k];
+    }
+    Out[base + i].has_tc = true;
+  }, fin_.size() >= 8192);
 }
 
 void GpuBackend_t::ResetCoverage() {

@@ -267,6 +267,16 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   bool classify(const std::vector<uint32_t> &pending, uint32_t first, const wtfgpu_exit_t *ex,
                 std::vector<uint8_t> &done, std::vector<LaneResult> *out, std::vector<uint32_t> &hits,
                 const uint64_t *stop_args = nullptr);
+  // What a lane's exit record is: a breakpoint hit for the host, still running,
+  // a StopWithArgs exit to be named, or the testcase's end. direct: the result
+  // went into *r, the view stayed untouched; ok: Stop(Ok) on an untouched view.
+  struct ExitClass {
+    enum Kind : uint8_t { Hit, Running, Named, Finished } kind;
+    bool direct = false, ok = false;
+  };
+  // the one reader of wtfgpu_exit_t::status; called inside HostPool loops, so it
+  // touches only lane l's view and touched_ flag, *r and the atomics of stats_
+  ExitClass classify_exit(uint32_t l, const wtfgpu_exit_t &e, LaneResult *r, bool direct_ok);
   // the device StopWithArgs exits of `named`: each lane's result from the kept arguments
   void name_stop_args(const std::vector<uint32_t> &named, uint32_t first, const wtfgpu_exit_t *ex,
                       std::vector<uint8_t> &done, std::vector<LaneResult> *out, const uint64_t *stop_args);
@@ -275,8 +285,8 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   // the final state of the finished lanes `fin` (registers and run stats read when wanted)
   bool fill_lanes(const std::vector<uint32_t> &fin, uint32_t first, const wtfgpu_exit_t *ex,
                   std::vector<LaneResult> &out);
-  // one finished lane's result, exit status, rip and retired count from its view and exit record
-  void fill_lane(uint32_t l, const wtfgpu_exit_t &e, LaneResult &r);
+  // one finished lane's result (direct: in r already, from classify_exit), exit status, rip and retired count
+  void fill_lane(uint32_t l, const wtfgpu_exit_t &e, LaneResult &r, bool direct = false);
   bool stop_prestopped(const std::vector<uint32_t> &lanes);
   void account_run(const wtfgpu_run_stats_t &rs);
   bool service_hits(const std::vector<uint32_t> &hits, uint32_t first, std::vector<uint8_t> &done, ModuleSlots *slots,
@@ -292,10 +302,8 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   // than `lanes` are skipped)
   void collect_coverage(const std::vector<uint32_t> &lanes, std::vector<LaneResult> &res,
                         const uint64_t *pf_hdr = nullptr);
-  // streaming state: slot occupancy, the caller's tag per lane, results
-  std::vector<uint8_t> busy_;
-  std::vector<uint64_t> tag_;
-  std::vector<uint64_t> tc_bytes_;  // the testcase size in each lane (B_exec)
+  // streaming state (set up with parts_): the caller's tag per lane, results
+  std::vector<uint64_t> tag_, tc_bytes_;  // tc_bytes_: the testcase size in each lane (B_exec)
   // lres_[l] is in its cleared state (Ok, no error, no coverage) unless the
   // lane is in its part's res_used list
   std::vector<LaneResult> lres_;
@@ -348,9 +356,8 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
     std::vector<uint32_t> occ, free;
     std::vector<uint32_t> res_used;  // lanes whose lres_ entry the last harvest handed out: cleared at the next
     wtfgpu_exit_t *ex = nullptr;  // the slice's exit records: pinned (one DMA of 40 B per lane)
-    uint64_t ex_cap = 0;
     uint8_t *pin = nullptr;
-    uint64_t pin_cap = 0;
+    uint64_t ex_cap = 0, pin_cap = 0;  // bytes
     // --device-mutate: the testcases the last harvest read back (lens and
     // offsets into the engine's pinned buffer of the part's queue, rb_bytes),
     // valid until the part's next harvest
@@ -361,18 +368,38 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
     std::vector<std::string> rb_tcs;  // --device-packets: the testcases made of the feeds read back
     // the slice's read-back queued behind it (wtfgpu_prefetch_results /
     // _coverage), pinned: byte and dirty-page counts, StopWithArgs
-    // arguments, the coverage entry count
+    // arguments, the coverage entry count (pf: set at each launch for that
+    // slice's harvest; false: the harvest reads them itself)
     bool pf = false, pf_cov = false;
     uint64_t *nb = nullptr, *sargs = nullptr, *cov_hdr = nullptr;
     uint32_t *dc = nullptr;
   };
-  bool prefetch_part(Part &P);
-  std::vector<Part> parts_;
+  std::vector<Part> parts_;  // empty until the first StreamStep (setup_parts)
   uint8_t *wpin_ = nullptr;  // pinned staging of host-handler writes (flush_lanes; applied synchronously)
   uint64_t wpin_cap_ = 0;
   uint32_t next_part_ = 0;
   uint32_t parts_n() const;
+  bool setup_parts();
+  void merge_lanes(std::vector<uint32_t> &into, const std::vector<uint32_t> &add);
+  template <class T>
+  bool fit_pinned(T *&p, uint64_t &cap, uint64_t need, uint64_t grow);
+  bool fit_exits(Part &P);
+  // StreamStep's refill of the fresh lanes (fresh_), in this order
+  void refill_pass(const std::vector<StreamTestcase_t> &In, ModuleSlots *Slots);
+  bool insert_unprepared(const Target_t &Target, const std::vector<StreamTestcase_t> &In, ModuleSlots *Slots);
+  bool list_ordered(const std::vector<StreamTestcase_t> &In);
+  bool upload_feeds(Part &P);
+  bool make_ordered();
+  bool prefetch_part(Part &P);
+  // a slice's harvest and its own phases, in this order
   bool harvest_part(Part &P, const Target_t &Target, std::vector<StreamResult_t> &Out, ModuleSlots *Slots);
+  void clear_results(Part &P);
+  uint64_t classify_part(Part &P);
+  uint64_t settle_late(Part &P);
+  void account_bytes(const Part &P, uint64_t prefetched);
+  void unplain_covered(Part &P);
+  bool read_back_kept(Part &P);
+  void write_out(Part &P, std::vector<StreamResult_t> &Out);
   void finish_coverage(uint32_t n, std::vector<LaneResult> *out, std::vector<uint32_t> *timedout);
   bool set_code_pages();
 
@@ -411,6 +438,7 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   std::vector<uint8_t> ordered_;
   std::vector<uint32_t> mut_lanes_, mut_nc_;
   std::vector<uint64_t> mut_idx_;
+  uint32_t min_entry_ = 0, min_op_ = 0;  // `minimize`: the one entry and op a step orders
   // --device-packets: on, and the target's declaration (the stream's params, FeedToTestcase)
   bool pkt_on_ = false;
   std::function<bool(const LaneResult &)> rb_keep_;  // SetReadbackFilter (empty: keep all)
