@@ -431,6 +431,20 @@ int wtfgpu_mutate_packets_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t
 #define WTFGPU_MIN_ZERO 1u   /* byte buffers: the range's bytes set to 0 */
 int wtfgpu_minimize_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t entry, uint32_t op,
                                const uint64_t *indices);
+/* The analyzer's candidates (`wtfgpu analyze`): lane lanes[i] gets candidate
+ * indices[i] over arena entry `entry`, as csrc/engine_analyze.h defines the
+ * stream: the entry with byte indices[i] / 4 replaced by variant
+ * indices[i] % 4 of it, in the two layouts wtfgpu_minimize_feed_lanes writes.
+ * A declared insert then runs on the same list, ordered after it.
+ * Asynchronous on the current queue; no caller's buffer is read after it
+ * returns. WTFGPU_ERR_INVALID, before anything is queued, for no arena, an
+ * `entry` at or above the entries added, a byte-buffer entry longer than
+ * WTFGPU_FEED_STRIDE - 4, an indices[i] at or above 4 * U (U: the entry's
+ * bytes, a feed's chunk bytes), on an arena of feeds an indices[i] whose
+ * position is one of a chunk's four Size bytes (framing), a lane outside the
+ * context or a null pointer. */
+int wtfgpu_analyze_feed_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t entry,
+                              const uint64_t *indices);
 /* The corpus distiller (`wtfgpu distill`): a greedy cover of n coverage sets,
  * as csrc/engine_distill.h defines the rule. Set i is the strictly ascending
  * values[offsets[i], offsets[i + 1]); eligible[i] == 0 leaves it out
@@ -492,6 +506,17 @@ int wtfgpu_collect_coverage_lanes(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32
 int wtfgpu_coverage_target(wtfgpu_ctx *ctx, const uint64_t *values, uint64_t n);
 int wtfgpu_coverage_contains(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint32_t *missing, uint32_t *size,
                              uint32_t *overflow);
+/* A set's signature (csrc/engine_analyze.h defines it): for each listed lane,
+ * sig[i] = the 64-bit wrap-around sum of mix64 over the values of the lane's
+ * whole coverage set, size[i] = the set's live entries and overflow[i] = 1
+ * when the set filled up (0 otherwise). Two lanes with equal (sig, size) ran
+ * the same path, without either set being read back. It waits for the current
+ * queue, reads the sets and does not empty them, so two calls in a row give
+ * the same answer. Before anything is queued: WTFGPU_ERR_INVALID for a null
+ * pointer with n > 0 or a lane outside the context; WTFGPU_ERR_STATE for a
+ * context without lanes or with coverage off. n == 0 is WTFGPU_OK. */
+int wtfgpu_coverage_signature(wtfgpu_ctx *ctx, const uint32_t *lanes, uint32_t n, uint64_t *sig, uint32_t *size,
+                              uint32_t *overflow);
 
 /* Bulk register I/O for lanes [first, first+count). */
 int wtfgpu_read_regs(wtfgpu_ctx *ctx, uint32_t first, uint32_t count, wtfgpu_regs_t *out);

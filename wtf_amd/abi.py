@@ -204,6 +204,9 @@ def load_hip_library(path: str = LIB_PATH) -> C.CDLL:
         "wtfgpu_minimize_feed_lanes": ([P, C.POINTER(U32), U32, U32, U32, C.POINTER(U64)], C.c_int),
         "wtfgpu_distill": ([P, U32, C.POINTER(U64), C.POINTER(U64), C.POINTER(C.c_uint8), C.POINTER(U32),
                             C.POINTER(U32), C.POINTER(U32), C.POINTER(U64)], C.c_int),
+        "wtfgpu_analyze_feed_lanes": ([P, C.POINTER(U32), U32, U32, C.POINTER(U64)], C.c_int),
+        "wtfgpu_coverage_signature": ([P, C.POINTER(U32), U32, C.POINTER(U64), C.POINTER(U32), C.POINTER(U32)],
+                                      C.c_int),
         "wtfgpu_coverage_target": ([P, C.POINTER(U64), U64], C.c_int),
         "wtfgpu_coverage_contains": ([P, C.POINTER(U32), U32, C.POINTER(U32), C.POINTER(U32), C.POINTER(U32)],
                                      C.c_int),

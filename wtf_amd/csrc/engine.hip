@@ -136,6 +136,10 @@ struct wtfgpu_ctx {
   // each entry's units (a byte buffer's bytes, a feed's packets): the index
   // check of wtfgpu_minimize_feed_lanes (engine_minimize.h)
   std::vector<u32> corpus_units;
+  // each feed entry's chunk offsets (coff[0 .. P], as the entry holds them):
+  // wtfgpu_analyze_feed_lanes refuses framing positions with them
+  // (engine_analyze.h); an arena of byte buffers keeps none
+  std::vector<std::vector<u32>> corpus_coff;
   // what the arena holds, fixed by its first add: byte buffers
   // (wtfgpu_corpus_add) or indexed feeds (wtfgpu_corpus_add_feed)
   enum CorpusKind : u32 { kCorpusEmpty, kCorpusBytes, kCorpusFeeds } corpus_kind = kCorpusEmpty;
@@ -1108,6 +1112,7 @@ int wtfgpu_corpus_alloc(wtfgpu_ctx *c, uint64_t max_entries, uint64_t max_bytes)
   c->corpus_max_entries = c->corpus_max_bytes = 0;
   c->corpus_off.clear();
   c->corpus_units.clear();
+  c->corpus_coff.clear();
   c->corpus_kind = wtfgpu_ctx::kCorpusEmpty;
   if (max_entries == 0) return WTFGPU_OK;
   if (dalloc(&c->d_corpus, max_bytes) || dalloc(&c->d_corpus_off, max_entries + 1)) {
@@ -1159,6 +1164,11 @@ int wtfgpu_corpus_add_feed(wtfgpu_ctx *c, const uint8_t *feed, uint64_t len, uin
   HIPCHK(hipMemcpy(c->d_corpus_off + count + 1, &end, 8, hipMemcpyHostToDevice));
   c->corpus_off.push_back(end);
   c->corpus_units.push_back((u32)packets);
+  {  // the entry's words 1 .. P + 1
+    std::vector<u32> coff((size_t)packets + 1);
+    memcpy(coff.data(), entry.data() + 4, coff.size() * 4);
+    c->corpus_coff.push_back(std::move(coff));
+  }
   c->corpus_kind = wtfgpu_ctx::kCorpusFeeds;
   if (index) *index = (u32)count;
   return WTFGPU_OK;
@@ -1384,6 +1394,49 @@ int wtfgpu_distill(wtfgpu_ctx *c, uint32_t n, const uint64_t *offsets, const uin
   for (u32 k = 0; k < st.kept; k++) out_index[k] = pick[out_index[k]];
   *kept = st.kept;
   *universe = U;
+  return WTFGPU_OK;
+}
+
+// The analyzer's candidates (engine_analyze.h): as wtfgpu_minimize_feed_lanes,
+// with the orders checked against the entry's length and, for a feed, against
+// the chunk offsets the host keeps (a framing position is refused).
+int wtfgpu_analyze_feed_lanes(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint32_t entry,
+                              const uint64_t *indices) {
+  if (!c || !c->d_gpr || !c->d_corpus || (n && (!lanes || !indices)) || entry >= c->corpus_units.size() ||
+      !lane_list_in_range(c, lanes, n))
+    return WTFGPU_ERR_INVALID;
+  const bool feeds = c->corpus_kind == wtfgpu_ctx::kCorpusFeeds;
+  if (feeds && entry >= c->corpus_coff.size()) return WTFGPU_ERR_INVALID;
+  u64 bytes = c->corpus_off[entry + 1] - c->corpus_off[entry];
+  // a byte buffer goes out as one chunk behind its u32 size: the kernel checks nothing
+  if (!feeds && bytes > WTFGPU_FEED_STRIDE - 4) return WTFGPU_ERR_INVALID;
+  {
+    const u32 *coff = feeds ? c->corpus_coff[entry].data() : nullptr;
+    const u32 P = feeds ? c->corpus_units[entry] : 0;
+    if (feeds) bytes = coff[P];
+    const u64 total = wtfana::total((u32)bytes);
+    u32 bad = 0;
+    for (u32 i = 0; i < n; i++)
+      bad |= (u32)(indices[i] >= total || (feeds && wtfana::is_framing(coff, P, (u32)(indices[i] >> 2))));
+    if (bad) return WTFGPU_ERR_INVALID;
+  }
+  if (n == 0) return WTFGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = feed_regions(c)) return rc;
+  Side s[] = {side_in(indices, (u64)n * 8)};
+  if (int rc = stage_lanes(c, Upload::Ring, lanes, n, s, 1)) return rc;
+  u8 *const S = c->q->d_scratch;
+  k_analyze_feeds<<<(n + MUT_WAVES - 1) / MUT_WAVES, 64 * MUT_WAVES, 0, c->q->stream>>>(
+      c->d_feeddata, c->feed_stride, (const u32 *)S, (const u64 *)(S + s[0].off), n, entry, feeds ? 1u : 0u,
+      c->d_corpus, c->d_corpus_off, c->d_feedpos, c->d_feedend);
+  HIPCHK(hipGetLastError());
+  c->P.feed_pos = c->d_feedpos;
+  c->P.feed_end = c->d_feedend;
+  c->P.feed_data = c->d_feeddata;
+  if (c->ins_on) {  // the declared insert of the listed lanes, ordered after the candidates
+    k_insert<<<(n + 63) / 64, 64, 0, c->q->stream>>>(c->P, c->ins, (const u32 *)S, 0, n);
+    HIPCHK(hipGetLastError());
+  }
   return WTFGPU_OK;
 }
 
@@ -2294,6 +2347,29 @@ int wtfgpu_coverage_contains(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, u
   HIPCHK(hipMemcpyAsync(missing, o, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
   HIPCHK(hipMemcpyAsync(size, o + n, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
   HIPCHK(hipMemcpyAsync(overflow, o + 2 * (u64)n, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipStreamSynchronize(c->q->stream));
+  return WTFGPU_OK;
+}
+
+// Each listed lane's set as a signature (k_cov_signature; engine_analyze.h);
+// the sets stay as they are.
+int wtfgpu_coverage_signature(wtfgpu_ctx *c, const uint32_t *lanes, uint32_t n, uint64_t *sig, uint32_t *size,
+                              uint32_t *overflow) {
+  if (!c || (n && (!lanes || !sig || !size || !overflow))) return WTFGPU_ERR_INVALID;
+  if (!c->d_gpr || !c->d_covrip) return WTFGPU_ERR_STATE;
+  if (!lane_list_in_range(c, lanes, n)) return WTFGPU_ERR_INVALID;
+  if (n == 0) return WTFGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  Side out = side_room((u64)n * 16);  // sig[n] | size[n] | overflow[n]
+  if (int rc = stage_lanes(c, Upload::Direct, lanes, n, &out, 1)) return rc;
+  u8 *const S = c->q->d_scratch;
+  u64 *const o = (u64 *)(S + out.off);
+  u32 *const o32 = (u32 *)(o + n);
+  k_cov_signature<<<(n + 3) / 4, 256, 0, c->q->stream>>>(c->P, (const u32 *)S, n, o, o32, o32 + n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(sig, o, (u64)n * 8, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipMemcpyAsync(size, o32, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
+  HIPCHK(hipMemcpyAsync(overflow, o32 + n, (u64)n * 4, hipMemcpyDeviceToHost, c->q->stream));
   HIPCHK(hipStreamSynchronize(c->q->stream));
   return WTFGPU_OK;
 }

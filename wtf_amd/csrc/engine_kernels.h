@@ -9,6 +9,7 @@
 #include "engine_minimize.h"
 #include "engine_distill.h"
 #include "engine_covkeep.h"
+#include "engine_analyze.h"
 #include "engine_feedpack.h"
 
 namespace {
@@ -721,6 +722,46 @@ __global__ __launch_bounds__(64 * MUT_WAVES) void k_minimize_feeds(u8 *feed, u64
   }
 }
 
+// The analyzer's candidates (wtfgpu_analyze_feed_lanes; engine_analyze.h
+// defines the stream): one wave per candidate, MUT_WAVES a block, four bytes a
+// lane a round, into the two layouts k_minimize_feeds writes. Candidate i is
+// the base (arena entry `entry`) with byte index[i] / 4 replaced by variant
+// index[i] % 4 of it, so the size is the base's and all 64 lanes share the
+// plan. The changed byte lies in exactly one destination word, and that word
+// is composed byte by byte, as is the last, partial word (zero-padded inside
+// the region: size <= stride - 4 for a byte buffer, the call refuses a longer
+// entry; size <= stride for a feed) and every word of a base that is not
+// 4-aligned in the arena; all other words are loaded whole. No LDS, and the
+// plan stays in registers.
+__global__ __launch_bounds__(64 * MUT_WAVES) void k_analyze_feeds(u8 *feed, u64 stride, const u32 *lanes,
+                                                                  const u64 *index, u32 n, u32 entry, u32 feeds,
+                                                                  const u8 *arena, const u64 *arena_off,
+                                                                  u64 *feed_pos, u64 *feed_end) {
+  const u32 i = blockIdx.x * MUT_WAVES + threadIdx.x / 64, l = threadIdx.x & 63;
+  if (i >= n) return;
+  const u32 lane = lanes[i];
+  wtfana::Plan p;
+  wtfana::make_plan(p, wtfmut::Corpus{arena, arena_off}, entry, feeds != 0, index[i]);
+  const u32 skip = feeds ? 0 : 4;
+  u8 *dst = feed + (u64)lane * stride;
+  if (l == 0) {
+    feed_pos[lane] = (u64)lane * stride;
+    feed_end[lane] = (u64)lane * stride + skip + p.size;
+    if (!feeds) *(u32 *)dst = p.size;
+  }
+  const bool aligned = ((u64)p.base & 3) == 0;
+  for (u32 j = 4 * l; j < p.size; j += 256) {
+    u32 w = 0;
+    if (aligned && j + 4 <= p.size && (p.p & ~3u) != j) {
+      w = *(const u32 *)(p.base + j);
+    } else {
+      for (u32 k = 0; k < 4; k++)
+        if (j + k < p.size) w |= (u32)wtfana::plan_byte(p, j + k) << (8 * k);
+    }
+    *(u32 *)(dst + skip + j) = w;
+  }
+}
+
 // wtfgpu_read_whole_feed_lanes: each listed lane's whole feed, from its
 // region's first byte to feed_end (which nothing moves after the feed is
 // written: k_run and k_insert advance feed_pos only), cut to `room` bytes, one
@@ -967,6 +1008,47 @@ __global__ __launch_bounds__(256) void k_cov_contains(Dev P, const u32 *lanes, u
   }
   if (lid) return;
   missing[i] = miss;
+  size[i] = cnt;
+  overflow[i] = P.cov_overflow[lane] ? 1u : 0u;
+}
+
+// ---- a set's signature (wtfgpu_coverage_signature; engine_analyze.h defines it)
+// For position i of the list: the wrap-around sum of mix64 over the values of
+// lane lanes[i]'s set, the set's live entries and its overflow flag. One wave
+// per position, four a block; the lane, its generation and its entry count are
+// the wave's. The wave strides over the lane's H slots 64 a step, gen then
+// rip, both coalesced; a thread adds mix64(rip) of its slot to a private sum
+// where the slot is live (gen == g). The ballot of "live" is the step's count,
+// the same in every thread, and the scan stops once the running count reaches
+// cov_cnt (the set's live slots, as log_value counts them). One 64-lane
+// shuffle reduction at the end. An empty set (cov_cnt 0) costs one load and
+// gives (0, 0). It reads the sets and changes nothing; the caller checked the
+// list.
+__global__ __launch_bounds__(256) void k_cov_signature(Dev P, const u32 *lanes, u32 n, u64 *sig, u32 *size,
+                                                       u32 *overflow) {
+  const u32 i = rfl32(blockIdx.x * 4 + (threadIdx.x >> 6)), lid = threadIdx.x & 63;
+  if (i >= n) return;
+  const u32 lane = rfl32(lanes[i]);
+  const u32 cnt = rfl32(P.cov_cnt[lane]);
+  u64 sum = 0;
+  if (cnt) {
+    const u32 g = rfl32(P.lane_gen[lane]), H = P.H;
+    const u64 *rip = P.cov_rip + (u64)lane * H;
+    const u32 *gen = P.cov_gen + (u64)lane * H;
+    u32 seen = 0;
+    for (u32 h0 = 0; h0 < H && seen < cnt; h0 += 64) {
+      const u32 h = h0 + lid;
+      const bool live = h < H && gen[h] == g;
+      if (live) sum += wtfkeep::mix64(rip[h]);
+      seen += (u32)__popcll(__ballot(live));
+    }
+    for (u32 d = 32; d; d >>= 1) {
+      const u32 lo = __shfl_xor((u32)sum, d, 64), hi = __shfl_xor((u32)(sum >> 32), d, 64);
+      sum += ((u64)hi << 32) | lo;
+    }
+  }
+  if (lid) return;
+  sig[i] = sum;
   size[i] = cnt;
   overflow[i] = P.cov_overflow[lane] ? 1u : 0u;
 }

@@ -231,6 +231,44 @@ class Engine:
         _chk(rc, "distill")
         return index, gain, universe
 
+    # ---- the analyzer's candidates and set signatures (csrc/engine_analyze.h)
+    def analyze_feed_lanes_rc(self, lanes, entry, indices) -> int:
+        """wtfgpu_analyze_feed_lanes' return code (asynchronous on the queue).
+        lanes / indices None: a null pointer."""
+        la = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.uint32)
+        ix = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint64)
+        n = len(la) if la is not None else len(ix)
+        assert la is None or ix is None or len(ix) == len(la)
+        return self.L.wtfgpu_analyze_feed_lanes(self.ctx,
+                                                None if la is None else la.ctypes.data_as(C.POINTER(C.c_uint32)), n,
+                                                entry,
+                                                None if ix is None else ix.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def analyze_feed_lanes(self, lanes, entry, indices):
+        _chk(self.analyze_feed_lanes_rc(lanes, entry, indices), "analyze_feed_lanes")
+
+    def coverage_signature_rc(self, lanes, want_out=True):
+        """wtfgpu_coverage_signature's return code and outputs: (rc, sig, size,
+        overflow), one entry a listed lane. lanes None: a null pointer (with
+        n = 1); want_out False: null output pointers."""
+        la = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.uint32)
+        n = 1 if la is None else len(la)
+        sig = np.zeros(max(n, 1), dtype=np.uint64)
+        out = [np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2)]
+        p32 = C.POINTER(C.c_uint32)
+        ptrs = [sig.ctypes.data_as(C.POINTER(C.c_uint64)) if want_out else None]
+        ptrs += [o.ctypes.data_as(p32) if want_out else None for o in out]
+        rc = self.L.wtfgpu_coverage_signature(self.ctx, None if la is None else la.ctypes.data_as(p32), n, *ptrs)
+        return (rc, sig[:n], out[0][:n], out[1][:n])
+
+    def coverage_signature(self, lanes):
+        """For each listed lane: its coverage set's signature (u64), the set's
+        entries and whether it overflowed (u32 arrays). The sets are not
+        emptied."""
+        rc, sig, size, overflow = self.coverage_signature_rc(lanes)
+        _chk(rc, "coverage_signature")
+        return sig, size, overflow
+
     # ---- keeping coverage (csrc/engine_covkeep.h)
     def coverage_target_rc(self, values) -> int:
         """wtfgpu_coverage_target's return code. values None: a null pointer

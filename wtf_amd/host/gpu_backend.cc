@@ -327,6 +327,13 @@ bool GpuBackend_t::DeviceCorpusAddFeed(const uint8_t *P, size_t N) {
   return pkt_on_ && wtfgpu_corpus_add_feed(ctx_, P, N, nullptr) == WTFGPU_OK;
 }
 
+// `analyze`: the minimiser's arena and orders, with the other kernel.
+bool GpuBackend_t::SetDeviceAnalyze(bool Feeds) {
+  if (!SetDeviceMinimize(Feeds)) return false;
+  ana_on_ = true;
+  return true;
+}
+
 // `minimize`: a small arena for the bases, one a round. Byte buffers reach the
 // guest through the declared insert, feeds through the Feed action: without
 // the one the target needs on the device, candidates made there go nowhere.
@@ -1257,7 +1264,7 @@ bool GpuBackend_t::service_hits(const std::vector<uint32_t> &hits, uint32_t firs
 // (bochscpu_backend.cc:501-504); timed-out lanes have theirs revoked
 // (client.cc:122-125); the new rips join the device coverage map.
 void GpuBackend_t::finish_coverage(uint32_t n, std::vector<LaneResult> *out, std::vector<uint32_t> *timedout) {
-  if (cov_target_ && out) {  // verdicts instead of sets (check_coverage)
+  if ((cov_target_ || cov_sig_) && out) {  // verdicts or signatures instead of sets (check_coverage)
     std::vector<uint32_t> all(n);
     for (uint32_t l = 0; l < n; l++) all[l] = l;
     last_new_coverage_.clear();
@@ -1343,13 +1350,18 @@ bool GpuBackend_t::check_coverage(const uint32_t *lanes, uint32_t n, std::vector
     keep_size_.resize(n);
     keep_ovf_.resize(n);
   }
-  const bool ok = wtfgpu_coverage_contains(ctx_, lanes, n, keep_missing_.data(), keep_size_.data(),
-                                           keep_ovf_.data()) == WTFGPU_OK &&
+  if (cov_sig_ && keep_sig_.size() < n) keep_sig_.resize(n);
+  // (a signature takes the place of the verdict: `analyze` sets no target)
+  const bool ok = (cov_sig_ ? wtfgpu_coverage_signature(ctx_, lanes, n, keep_sig_.data(), keep_size_.data(),
+                                                        keep_ovf_.data())
+                            : wtfgpu_coverage_contains(ctx_, lanes, n, keep_missing_.data(), keep_size_.data(),
+                                                       keep_ovf_.data())) == WTFGPU_OK &&
                   wtfgpu_clear_coverage_lanes(ctx_, lanes, n) == WTFGPU_OK;
   for (uint32_t i = 0; i < n; i++) {
     LaneResult &r = res[lanes[i]];
     r.new_coverage.clear();
-    r.cov_missing = ok ? keep_missing_[i] : ~0u;
+    r.cov_sig = ok && cov_sig_ ? keep_sig_[i] : 0;
+    r.cov_missing = ok && !cov_sig_ ? keep_missing_[i] : ~0u;
     r.cov_size = ok ? keep_size_[i] : 0;
     r.cov_overflow = ok && keep_ovf_[i] != 0;
   }
@@ -1359,6 +1371,16 @@ bool GpuBackend_t::check_coverage(const uint32_t *lanes, uint32_t n, std::vector
   }
   stats_.covlog_ms += ms_since(t0);
   return ok;
+}
+
+// `analyze` (csrc/engine_analyze.h): signatures instead of sets, by the same
+// route as the verdicts above. Full coverage stays on from then on.
+bool GpuBackend_t::SetCoverageSignature(bool On) {
+  if (!ctx_) return false;
+  if (On) full_coverage_ = true;
+  cov_sig_ = On;
+  cov_check_failed_ = false;
+  return true;
 }
 
 // Whole sets read back in a call that reported an overflow: the sets that
@@ -1603,7 +1625,7 @@ void GpuBackend_t::apply_attribution(const uint32_t *lanes, uint64_t total, std:
 // device map. Their log bits are dropped (the lanes get new testcases next).
 void GpuBackend_t::collect_coverage(const std::vector<uint32_t> &lanes, std::vector<LaneResult> &res,
                                     const uint64_t *pf_hdr) {
-  if (cov_target_) {  // verdicts instead of sets: no reader below runs
+  if (cov_target_ || cov_sig_) {  // verdicts or signatures instead of sets: no reader below runs
     last_new_coverage_.clear();
     cov_sorted_.clear();
     check_coverage(lanes.data(), (uint32_t)lanes.size(), res);
@@ -1959,7 +1981,7 @@ bool GpuBackend_t::list_ordered(const std::vector<StreamTestcase_t> &In) {
   if (mut_on_ || pkt_on_ || min_on_)
     for (size_t i = 0; i < fresh_.size(); i++)
       if (In[i].ordered) {
-        if (In[i].minimize != min_on_) return false;
+        if ((In[i].minimize || In[i].analyze) != min_on_ || In[i].analyze != ana_on_) return false;
         if (min_on_ && !mut_lanes_.empty() && (In[i].min_entry != min_entry_ || In[i].min_op != min_op_)) return false;
         min_entry_ = In[i].min_entry;
         min_op_ = In[i].min_op;
@@ -2014,7 +2036,9 @@ bool GpuBackend_t::make_ordered() {
   const auto tmu = Clock::now();
   const uint32_t m = (uint32_t)mut_lanes_.size();
   int rc;
-  if (min_on_) {
+  if (ana_on_) {
+    rc = wtfgpu_analyze_feed_lanes(ctx_, mut_lanes_.data(), m, min_entry_, mut_idx_.data());
+  } else if (min_on_) {
     rc = wtfgpu_minimize_feed_lanes(ctx_, mut_lanes_.data(), m, min_entry_, min_op_, mut_idx_.data());
   } else if (pkt_on_) {
     const wtfgpu_packet_params_t pp{pkt_.GenMaxPackets, pkt_.GenCommands, pkt_.GenMaxBody, pkt_.FlipOneIn,
@@ -2051,7 +2075,7 @@ bool GpuBackend_t::prefetch_part(Part &P) {
     return false;
   if (wtfgpu_prefetch_results(ctx_, P.lo, count, P.ex, P.nb, P.dc, args ? P.sargs : nullptr) != WTFGPU_OK)
     return false;
-  P.pf_cov = !full_coverage_ && !device_attrib_ && !cov_target_ &&
+  P.pf_cov = !full_coverage_ && !device_attrib_ && !cov_target_ && !cov_sig_ &&
              wtfgpu_prefetch_coverage(ctx_, P.lo, count, P.cov_hdr) == WTFGPU_OK;
   return true;
 }
@@ -2112,6 +2136,7 @@ void GpuBackend_t::clear_results(Part &P) {
     r.new_coverage.clear();
     r.cov_missing = ~0u;
     r.cov_size = 0;
+    r.cov_sig = 0;
     r.cov_overflow = false;
   }, P.res_used.size() >= 8192);
   P.res_used.clear();
@@ -2134,7 +2159,7 @@ uint64_t GpuBackend_t::classify_part(Part &P) {
   const bool fill = !want_gprs_;
   // with a coverage target every finished lane gets a LaneResult: the verdict
   // goes into it (no counted nullptr results in that mode)
-  const bool counted = fill && !cov_target_;
+  const bool counted = fill && !cov_target_ && !cov_sig_;
   HostPool::Get().For(chunks, 1, [&](size_t c) {
     HarvestChunk &C = hchunks_[c];
     C.fin.clear();

@@ -148,6 +148,18 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   bool HasDeviceCoverageCheck() const override { return true; }
   bool SetCoverageTarget(const uint64_t *Values, size_t N) override;
   void ClearCoverageTarget() override { cov_target_ = false; }
+  // `analyze`: the minimiser's arena and refill with wtfgpu_analyze_feed_lanes
+  // (StreamTestcase_t::analyze), and, while the signature switch is on, each
+  // finished lane's set as a signature (wtfgpu_coverage_signature) by the
+  // route the verdicts above take: no set reader runs, every finished lane
+  // gets a LaneResult, full coverage stays on
+  bool HasDeviceAnalyzer() const override { return true; }
+  bool SetDeviceAnalyze(bool Feeds) override;
+  bool DeviceAnalyzeBase(const uint8_t *P, size_t N, uint32_t *Entry) override {
+    return ana_on_ && DeviceMinimizeBase(P, N, Entry);
+  }
+  bool HasDeviceCoverageSignature() const override { return true; }
+  bool SetCoverageSignature(bool On) override;
   uint32_t FreeLanes() const override;
   bool StreamStep(const Target_t &Target, const std::vector<StreamTestcase_t> &In, uint64_t Slice,
                   std::vector<StreamResult_t> &Out, ModuleSlots *Slots, size_t *Taken) override;
@@ -337,6 +349,8 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   std::vector<std::pair<uint32_t, uint64_t>> cov_sorted_;  // the same, sorted by (lane, rip)
   bool cov_ovf_warned_ = false;
   bool cov_target_ = false;  // SetCoverageTarget: verdicts instead of sets
+  bool cov_sig_ = false;     // SetCoverageSignature: signatures instead of sets
+  std::vector<uint64_t> keep_sig_;
   bool cov_check_failed_ = false;
   uint32_t cov_set_ = 0;     // a lane's coverage set slots (Options_t::GpuCoverageSet)
   std::vector<uint32_t> keep_missing_, keep_size_, keep_ovf_;  // wtfgpu_coverage_contains' answers
@@ -445,6 +459,7 @@ class GpuBackend_t final : public Backend_t, public Executor_t {
   PacketMutator_t pkt_{};
   // `minimize`: on, and whether the arena holds feeds (else byte buffers)
   bool min_on_ = false, min_feeds_ = false;
+  bool ana_on_ = false;  // `analyze`: min_on_ with the analyzer's candidates
   bool insert_action_ = false;                   // the declared insert is on the device (wtfgpu_set_insert)
   int upload_feed(uint32_t n);                   // lanes [0, n)
   std::unordered_set<uint64_t> aggregate_;

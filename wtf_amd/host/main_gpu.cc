@@ -13,6 +13,10 @@
 //   wtfgpu distill --name tlv_server --target targets/tlv [--input targets/tlv/outputs] --output kept/
 //       [--results f] [--lanes 4096] [--limit l] [--edges] [--cov-set 8192]   (copies a covering subset of a
 //       corpus: greedy cover on the GPU, WTFGPU_DISTILL_HOST=1 runs it on the host instead: distill.cc)
+//   wtfgpu analyze --name hevd --target targets/hevd --input f [--output f.map] [--lanes 4096] [--edges] [--cov-set n]
+//       (what each byte of f does: every byte's four one-byte variants run and compared by outcome and coverage
+//       signature; candidates and signatures made on the GPU, WTFGPU_ANALYZE_HOST=1 / WTFGPU_COVSIG_HOST=1 move
+//       either to the host: analyze.cc)
 // The same runner drives the oracle twin (oracle/twin_backend.cc) for parity.
 #include <cstdio>
 #include <memory>

@@ -232,7 +232,7 @@ void PrintTestcaseRunStats(const LaneResult &L, size_t AggregateCoverage) {
 }
 
 bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
-  bool Minimize = false, Distill = false;
+  bool Minimize = false, Distill = false, Analyze = false;
   int ModeWords = 0;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -246,6 +246,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     if (a == "run" || a == "fuzz" || a == "master") O.mode = a, ModeWords++;
     else if (a == "minimize") Minimize = true;
     else if (a == "distill") Distill = true;
+    else if (a == "analyze") Analyze = true;
     else if (a == "--cov-set") O.cov_set = (uint32_t)strtoul(next("--cov-set"), nullptr, 0);
     else if (a == "--output") O.output = next("--output");
     else if (a == "--rounds") O.rounds = strtoull(next("--rounds"), nullptr, 0);
@@ -322,6 +323,22 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     }
     O.mode = "minimize";
   }
+  if (Analyze) {
+    if (Minimize || Distill || ModeWords || !O.address.empty() || O.world > 1 || !O.module_so.empty()) {
+      fprintf(stderr, "analyze is one in-process session: not with master (or another mode), --address, --world > 1 "
+                      "or --module-so\n");
+      return false;
+    }
+    if (O.input.empty()) {
+      fprintf(stderr, "analyze needs --input <testcase>\n");
+      return false;
+    }
+    if (O.cov_set == 0) {
+      fprintf(stderr, "analyze: --cov-set must be at least 1\n");
+      return false;
+    }
+    O.mode = "analyze";
+  }
   if (Distill) {
     if (Minimize || ModeWords || !O.address.empty() || O.world > 1 || !O.module_so.empty()) {
       fprintf(stderr, "distill is one in-process session: not with master (or another mode), --address, --world > 1 "
@@ -361,7 +378,7 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
     }
   }
   if (O.name.empty() || O.target.empty()) {
-    fprintf(stderr, "usage: [run|fuzz|master|minimize|distill] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
+    fprintf(stderr, "usage: [run|fuzz|master|minimize|distill|analyze] --name <target> --target <dir> [--input p] [--results f] [--limit n]\n"
                     "       [--lanes n] [--overlay-pages k] [--spill-pages s [--spill-lane-max x]] [--runs n] [--seconds s] [--seed s] [--full-coverage]\n"
                     "       [--serial-mutation] [--slice-steps s] [--regroup-steps r] [--rank r --world n [--exchange host:port | --nccl-id-file f]]\n"
                     "       [--address tcp://ip:port|unix://path [--batched] [--nodes k]] [--edges] [--device-attrib] [--device-mutate]\n"
@@ -369,7 +386,8 @@ bool ParseRunnerArgs(int argc, char **argv, RunnerOptions &O) {
                     "       [--trace-path dir [--trace-type rip|cov|tenet] [--trace-cap n] [--tenet-cap bytes]] [--module-so m.so] [--serial]\n"
                     "       minimize: --input <crashing testcase> [--output f] [--lanes n] [--limit l] [--rounds r]\n"
                     "                 [--keep-coverage [--edges] [--cov-set n]] (--input: a testcase that ends ok)\n"
-                    "       distill: [--input dir] --output <dir> [--results f] [--lanes n] [--limit l] [--edges] [--cov-set n]\n");
+                    "       distill: [--input dir] --output <dir> [--results f] [--lanes n] [--limit l] [--edges] [--cov-set n]\n"
+                    "       analyze: --input <testcase> [--output f.map] [--lanes n] [--limit l] [--edges] [--cov-set n]\n");
     return false;
   }
   return true;
@@ -394,6 +412,7 @@ bool LoadTarget(const RunnerOptions &O, Options_t &Opts, CpuState_t &State) {
   if (O.full_coverage || (O.mode == "run" && O.stream_run)) Opts.GpuCoverageSet = 8192;
   if (O.mode == "distill") Opts.GpuCoverageSet = O.cov_set;  // whole sets too, sized by --cov-set
   if (O.mode == "minimize" && O.keep_coverage) Opts.GpuCoverageSet = O.cov_set;  // likewise
+  if (O.mode == "analyze") Opts.GpuCoverageSet = O.cov_set;                       // likewise
   Opts.Fuzz.Seed = (uint32_t)O.seed;
   if (!LoadCpuStateFromJSON(State, Opts.CpuStatePath)) {
     printf("Failed to load the CPU state from %s\n", Opts.CpuStatePath.string().c_str());
@@ -678,6 +697,7 @@ int RunnerMain(const RunnerOptions &O, Executor_t &Exec, const Options_t &Opts, 
 
   if (O.mode == "minimize") return MinimizeMain(O, Exec, *Target, Slots);
   if (O.mode == "distill") return DistillMain(O, Exec, *Target, Slots);
+  if (O.mode == "analyze") return AnalyzeMain(O, Exec, *Target, Slots);
 
   // ---- fuzz against a remote master (wire.h): the client loop
   if (!O.address.empty()) return NodeMain(O, Exec, *Target, Slots);

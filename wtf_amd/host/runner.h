@@ -49,6 +49,11 @@ struct LaneResult {
   // reports whole sets and knows this one filled up.
   uint32_t cov_missing = ~0u, cov_size = 0;
   bool cov_overflow = false;
+  // `analyze` on an executor with the signature switch on
+  // (SetCoverageSignature): the signature of the testcase's whole set
+  // (csrc/engine_analyze.h) with cov_size and cov_overflow, instead of
+  // new_coverage
+  uint64_t cov_sig = 0;
 };
 
 struct StreamTestcase_t {
@@ -71,6 +76,10 @@ struct StreamTestcase_t {
   // order of one step names the same entry and op.
   bool minimize = false;
   uint32_t min_entry = 0, min_op = 0;
+  // `analyze` on an executor with the device analyzer: an ordered testcase
+  // that is candidate `index` (csrc/engine_analyze.h) over the base
+  // DeviceAnalyzeBase gave `min_entry` for
+  bool analyze = false;
 };
 // A finished testcase: its tag and its result, which stays in the executor's
 // storage and is valid until the executor's next StreamStep (no per-result
@@ -174,6 +183,20 @@ class Executor_t {
   virtual bool HasDeviceCoverageCheck() const { return false; }
   virtual bool SetCoverageTarget(const uint64_t * /*Values*/, size_t /*N*/) { return false; }
   virtual void ClearCoverageTarget() {}
+  // `analyze`: true = this executor makes the candidates itself
+  // (StreamTestcase_t::analyze) from the base it is given once, as the device
+  // minimiser does; Feeds as there. Default: the session materialises.
+  virtual bool HasDeviceAnalyzer() const { return false; }
+  virtual bool SetDeviceAnalyze(bool /*Feeds*/) { return false; }
+  virtual bool DeviceAnalyzeBase(const uint8_t *, size_t, uint32_t * /*Entry*/) { return false; }
+  // `analyze`: true = this executor answers with a signature of the testcase's
+  // whole coverage set (csrc/engine_analyze.h). While the switch is on, every
+  // finished testcase comes back with a LaneResult (never the counted nullptr
+  // of StreamResult_t) whose cov_sig / cov_size / cov_overflow are filled and
+  // whose new_coverage is empty: no set is read back. Default: the session
+  // computes signatures from new_coverage.
+  virtual bool HasDeviceCoverageSignature() const { return false; }
+  virtual bool SetCoverageSignature(bool /*On*/) { return false; }
   // Which ordered results the session wants bytes for (KeepsTestcase over its
   // own state): an executor that mutates on the device reads back only those
   // and sets StreamResult_t::has_tc on them. Called during StreamStep, on any
@@ -296,7 +319,7 @@ class CoverageExchange_t {
 void PrintTestcaseRunStats(const LaneResult &L, size_t AggregateCoverage);
 
 struct RunnerOptions {
-  std::string mode = "run";  // run | fuzz | master | minimize | distill
+  std::string mode = "run";  // run | fuzz | master | analyze | minimize | distill
   std::string name;          // target name
   std::string target;        // dir with state/, inputs/, outputs/, crashes/
   std::string input;         // run: file or directory (default <target>/inputs)
@@ -591,6 +614,11 @@ class FuzzSession {
 // (csrc/engine_covkeep.h), checked on the device where the executor can.
 // Returns the exit code.
 int MinimizeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, ModuleSlots &Slots);
+// `analyze` (analyze.cc): what each byte of O.input does, by the rule of
+// csrc/engine_analyze.h: every position's four one-byte variants are run and
+// compared with the input's own outcome; candidates are made and coverage
+// sets compared on the device where the executor can. Returns the exit code.
+int AnalyzeMain(const RunnerOptions &O, Executor_t &Exec, Target_t &Target, ModuleSlots &Slots);
 // `distill` (distill.cc): replays the inputs for their whole coverage sets and
 // copies a covering subset, chosen by the greedy cover of
 // csrc/engine_distill.h, into O.output; the cover runs on the device where the
